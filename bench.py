@@ -14,13 +14,30 @@ from RANK/LOCAL_RANK/WORLD_SIZE/MASTER_*.)
 
 Rank 0 prints ONE JSON line: whole-job samples/sec over exactly K timed
 steps bracketed by barrier+synchronize on both sides, MAX time over ranks.
+
+A plain run does only what that line needs: set up, warm up, time the K
+steps, print. ``--dump-outputs DIR`` additionally writes what the last
+timed step computed (its loss, the updated weights) as ``DIR/*.npy`` so
+two builds can be compared output for output; ``--full`` adds what
+the headline does not need (see its help text).
 """
 from __future__ import annotations
 
 import argparse
 import json
 import os
+import tempfile
 import time
+
+# MIOpen's find (cudnn.benchmark, required by the graphed step) times every
+# applicable solver for each conv, among them the reference "naive" direct
+# solvers: always applicable, never the winner, and so slow to run on the
+# bs-212 shapes that they cost ~15 s of start-up. Masking them changes no
+# selected kernel (measured: same step time, outputs within run-to-run
+# noise). Set before the first conv; an explicit setting in the
+# environment wins.
+for _d in ("FWD", "BWD", "WRW"):
+    os.environ.setdefault(f"MIOPEN_DEBUG_CONV_DIRECT_NAIVE_CONV_{_d}", "0")
 
 import torch
 import torch.distributed as dist
@@ -31,14 +48,45 @@ from mi355x_scale.train.datamodule import ImageStreamDataModule
 from mi355x_scale.train.trainer import _TrainStepShim
 from torch.nn.parallel import DistributedDataParallel as DDP
 
-DATA_DIR = os.environ.get("MI355X_BENCH_DATA", "/tmp/mi355x_bench_data")
+# per-user default: a directory another account left behind in the shared
+# temp dir would not be writable
+DATA_DIR = os.environ.get(
+    "MI355X_BENCH_DATA",
+    os.path.join(tempfile.gettempdir(), f"mi355x_bench_data_{os.getuid()}"))
+
+# --dump-outputs budget: at most this many float32 elements per array
+# (48 MiB, under the 64 MB a dump may take in all; ResNet-18's 11.7M
+# weights fit whole, larger models are sampled)
+DUMP_MAX_ELEMS = 12 * 1024 * 1024
+
+# With cudnn.benchmark MIOpen also TUNES every tunable solver the first
+# time it meets a conv shape (results persist in the user's MIOpen db, so
+# only a first run pays). For ResNet-18's ten conv shapes at bs 212 the
+# winners are fixed: composable-kernel grouped fwd, asm dynamic igemm bwd
+# and wrw. The composable-kernel bwd/wrw solvers and the asm igemm fwd
+# solver lose every one of those finds (1.1-1.7x, ~2x and 1.3-1.6x slower
+# after tuning), yet tuning their 1560 + 2080 + 634 configurations is
+# ~12 s of a first start. Masking them selects the same kernels without
+# that search.
+# NOTE the middle entry: with the MIOpen of ROCm 7.0 that variable masks
+# its solver when set to 1 and does nothing at 0 (checked by counting the
+# tuning searches in MIOpen's log). On a MIOpen where it reads the usual
+# way round, 1 is the default and only the saving is lost.
+RESNET18_LOSING_SOLVERS = {
+    "MIOPEN_DEBUG_CONV_IMPLICIT_GEMM_ASM_FWD_GTC_XDLOPS_NHWC": "0",
+    "MIOPEN_DEBUG_CONV_IMPLICIT_GEMM_HIP_GROUP_BWD_XDLOPS": "1",
+    "MIOPEN_DEBUG_GROUP_CONV_IMPLICIT_GEMM_HIP_WRW_XDLOPS": "0",
+}
 
 
 def prepare_data(rows: int, image_hw, rank: int, world: int,
                  rpg: int = 256) -> str:
     from mi355x_scale.data.generator import write_image_parquet
-    marker = os.path.join(DATA_DIR, ".complete")
+    # one directory per dataset shape: runs of different sizes (plain vs
+    # --full, CPU vs GPU config) never invalidate each other's data
     tag = f"{rows}x{image_hw[0]}x{rpg}"
+    data_dir = os.path.join(DATA_DIR, tag)
+    marker = os.path.join(data_dir, ".complete")
     if rank == 0:
         ok = False
         if os.path.exists(marker):
@@ -46,15 +94,49 @@ def prepare_data(rows: int, image_hw, rank: int, world: int,
                 ok = f.read().strip() == tag
         if not ok:
             import shutil
-            shutil.rmtree(DATA_DIR, ignore_errors=True)
+            shutil.rmtree(data_dir, ignore_errors=True)
             # row group == one training batch: the DataLoader slices whole
             # groups zero-copy (no carry concatenation on the hot path)
-            write_image_parquet(DATA_DIR, num_rows=rows, image_hw=image_hw,
+            write_image_parquet(data_dir, num_rows=rows, image_hw=image_hw,
                                 rows_per_group=rpg, rows_per_file=rpg * 5)
             with open(marker, "w") as f:
                 f.write(tag)
     barrier()
-    return DATA_DIR
+    return data_dir
+
+
+def _sample_f32(flat: torch.Tensor):
+    """float32 numpy copy of a flat tensor; above DUMP_MAX_ELEMS a fixed,
+    seeded, sorted sample of its elements (same indices every run)."""
+    import numpy as np
+    flat = flat.detach().reshape(-1)
+    n = flat.numel()
+    if n > DUMP_MAX_ELEMS:
+        idx = np.sort(np.random.default_rng(0).choice(
+            n, size=DUMP_MAX_ELEMS, replace=False))
+        flat = flat[torch.from_numpy(idx).to(flat.device)]
+    return flat.float().cpu().numpy()
+
+
+def dump_outputs(out_dir: str, loss: torch.Tensor, model) -> None:
+    """Write what the last timed step handed back to its caller: the loss
+    it returned and the model weights after its optimizer update, as one
+    flat array in ``model.parameters()`` order (the values the next
+    forward would use: bf16 working copies where the optimizer keeps
+    them). Gradients are left out on purpose: on this random-image,
+    random-label data they are cancellation residue of magnitude ~1e-7
+    whose value differs by 10-20% between two runs of the same build, so
+    they cannot tell two builds apart."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    params = [p for p in model.parameters() if p.requires_grad]
+    arrays = {
+        "loss": loss.detach().float().reshape(1).cpu().numpy(),
+        "params": _sample_f32(torch.cat(
+            [p.detach().float().reshape(-1) for p in params])),
+    }
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
 
 
 def main() -> None:
@@ -76,7 +158,24 @@ def main() -> None:
     ap.add_argument("--timing", action="store_true",
                     help="print per-step loader-wait vs compute breakdown "
                          "to stderr")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's "
+                         "loss and the updated weights as "
+                         "DIR/<name>.npy (float32). The streaming loader "
+                         "then runs one decode thread and one stager so "
+                         "the batch order, hence every output, is the "
+                         "same from run to run")
+    ap.add_argument("--full", action="store_true",
+                    help="do what the headline figure of this run does not "
+                         "need: size the dataset for the largest world "
+                         "(8 ranks) whatever --gpus is, so that an "
+                         "N=1,2,4,8 sweep generates it once and every N "
+                         "streams the same files")
     args = ap.parse_args()
+
+    if args.model == "resnet18":  # measured for this model's shapes only
+        for var, val in RESNET18_LOSING_SOLVERS.items():
+            os.environ.setdefault(var, val)
 
     use_cuda = torch.cuda.is_available()
     if use_cuda:
@@ -96,11 +195,13 @@ def main() -> None:
     data_dir = None
     if not args.resident:
         rpg = batch if use_cuda else 16
-        # size the dataset for the LARGEST world (8) regardless of N so
-        # the driver's N=1,2,4,8 sequence generates the parquet once and
-        # reuses it (the reader is infinite; extra rows just mean more
-        # distinct batches per shard)
-        rows = max(args.rows, 20 * rpg * (8 if use_cuda else n_gpus))
+        # 20 distinct batches per rank (the reader is infinite; extra rows
+        # just mean more distinct batches per shard). --full sizes for
+        # the LARGEST world (8) regardless of N so an N=1,2,4,8 sequence
+        # generates the parquet once and reuses it; a plain run writes
+        # only what its own ranks stream
+        sized_for = 8 if (use_cuda and args.full) else n_gpus
+        rows = max(args.rows, 20 * rpg * sized_for)
         rows = (rows // rpg) * rpg
         data_dir = prepare_data(rows, image_hw, ctx.rank, n_gpus, rpg=rpg)
 
@@ -140,6 +241,13 @@ def main() -> None:
         }
         it = iter(lambda: fixed, None)  # infinite
     else:
+        stagers = 3
+        if args.dump_outputs:
+            # decode threads and stagers race for the next row group, so
+            # with several of them the batch order differs from run to
+            # run; one of each streams the row groups in file order
+            args.workers_count = 1
+            stagers = 1
         dm = ImageStreamDataModule(
             data_dir, batch_size=batch,
             workers_count=args.workers_count,
@@ -147,7 +255,7 @@ def main() -> None:
             cur_shard=ctx.rank if n_gpus > 1 else None,
             shard_count=n_gpus if n_gpus > 1 else None,
             image_hw=image_hw, device=device,
-            prefetch_depth=3, stagers=3,
+            prefetch_depth=3, stagers=stagers,
         )
         loader = dm.train_dataloader()  # infinite reader
         it = iter(loader)
@@ -193,12 +301,16 @@ def main() -> None:
     if use_cuda:
         torch.cuda.synchronize()
     t0 = time.perf_counter()
+    loss = None
     for _ in range(args.steps):
-        one_step()
+        loss = one_step()
     if use_cuda:
         torch.cuda.synchronize()
     barrier()
     elapsed = time.perf_counter() - t0
+
+    if args.dump_outputs and ctx.rank == 0 and loss is not None:
+        dump_outputs(args.dump_outputs, loss, model)
 
     # MAX over ranks
     t = torch.tensor([elapsed], dtype=torch.float64,

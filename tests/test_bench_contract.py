@@ -19,6 +19,10 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def _run_bench(extra, env_extra=None, timeout=420):
     env = dict(os.environ)
     env.setdefault("MASTER_ADDR", "127.0.0.1")
+    # these are CPU rehearsals (they assert the CPU smoke config): hide any
+    # GPU from the child so they mean the same on a GPU box
+    env["HIP_VISIBLE_DEVICES"] = ""
+    env["CUDA_VISIBLE_DEVICES"] = ""
     if env_extra:
         env.update(env_extra)
     res = subprocess.run(extra, capture_output=True, text=True,
@@ -49,6 +53,36 @@ def test_bench_single_process_contract():
     out = _run_bench([sys.executable, "bench.py", "--steps", "2",
                       "--warmup", "1"])
     _check_contract(out, 1)
+
+
+def test_bench_dump_outputs_repeatable(tmp_path):
+    """--dump-outputs writes the last timed step's loss and the updated
+    weights as float32 .npy, and two runs with the same arguments see the
+    same inputs, so (on CPU, same thread count) the dumps are bit-identical.
+    The second run adds --full, which must be accepted and, in the CPU
+    config, changes no input."""
+    import numpy as np
+    dumps = []
+    for name, extra in (("a", []), ("b", ["--full"])):
+        d = tmp_path / name
+        out = _run_bench([sys.executable, "bench.py", "--steps", "3",
+                          "--warmup", "1", "--dump-outputs", str(d)] + extra)
+        _check_contract(out, 1)
+        assert out["steps"] == 3 and out["ms_per_step"] > 0
+        files = sorted(p.name for p in d.iterdir())
+        assert files == ["loss.npy", "params.npy"]
+        dumps.append({p.stem: np.load(p) for p in d.iterdir()})
+    a, b = dumps
+    total = 0
+    for k in a:
+        assert a[k].dtype == np.float32
+        assert np.isfinite(a[k]).all()
+        assert np.array_equal(a[k], b[k]), k
+        total += a[k].nbytes
+    assert total <= 64 * 1024 * 1024
+    assert a["loss"].shape == (1,)
+    # resnet18: 11,689,512 trainable weights, dumped whole
+    assert a["params"].shape == (11_689_512,)
 
 
 @pytest.mark.timeout(600)
