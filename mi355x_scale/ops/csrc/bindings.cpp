@@ -177,7 +177,19 @@ extern "C" void launch_bn_fwd_finalize(const float* partial, int nblocks,
                                        float* running_mean,
                                        float* running_var, float momentum,
                                        float eps, long long rows, int C,
-                                       int update_running, hipStream_t stream);
+                                       int update_running,
+                                       long long* num_batches_tracked,
+                                       hipStream_t stream);
+extern "C" void launch_bn_pool_bwd_reduce(
+    const void* dp, const unsigned char* code, const void* x,
+    const float* mean, const float* invstd, const float* weight,
+    const float* bias, float* partial, int nblocks, int N, int H, int W,
+    int Ho, int Wo, int C, hipStream_t stream);
+extern "C" void launch_bn_pool_bwd_apply(
+    const void* dp, const unsigned char* code, const void* x,
+    const float* mean, const float* invstd, const float* bias,
+    const float* k, void* dx, int N, int H, int W, int Ho, int Wo, int C,
+    hipStream_t stream);
 extern "C" void launch_bn_fwd_apply(const void* x, const void* res, void* y,
                                     const float* mean, const float* invstd,
                                     const float* weight, const float* bias,
@@ -248,19 +260,30 @@ torch::Tensor bn_fwd_reduce(torch::Tensor x, int64_t C) {
 void bn_fwd_finalize(torch::Tensor partial, torch::Tensor mean,
                      torch::Tensor invstd, torch::Tensor running_mean,
                      torch::Tensor running_var, double momentum, double eps,
-                     int64_t rows, int64_t C, bool update_running) {
+                     int64_t rows, int64_t C, bool update_running,
+                     c10::optional<torch::Tensor> num_batches_tracked) {
   _check_f32(partial, "partial"); _check_f32(mean, "mean");
   _check_f32(invstd, "invstd");
   _check_f32(running_mean, "running_mean");
   _check_f32(running_var, "running_var");
   TORCH_CHECK(partial.numel() % (2 * C) == 0, "partial must be [nb*2C]");
   int nb = (int)(partial.numel() / (2 * C));
+  // optional module step counter, bumped by the kernel (saves the
+  // standalone `num_batches_tracked += 1` dispatch per BN)
+  long long* nbt_p = nullptr;
+  if (num_batches_tracked.has_value()) {
+    const torch::Tensor& nbt = *num_batches_tracked;
+    TORCH_CHECK(nbt.is_cuda() && nbt.scalar_type() == torch::kInt64 &&
+                    nbt.numel() == 1,
+                "num_batches_tracked must be a 1-element int64 GPU tensor");
+    nbt_p = reinterpret_cast<long long*>(nbt.data_ptr<int64_t>());
+  }
   launch_bn_fwd_finalize(partial.data_ptr<float>(), nb,
                          mean.data_ptr<float>(), invstd.data_ptr<float>(),
                          running_mean.data_ptr<float>(),
                          running_var.data_ptr<float>(), (float)momentum,
                          (float)eps, rows, (int)C, update_running ? 1 : 0,
-                         at::cuda::getCurrentHIPStream().stream());
+                         nbt_p, at::cuda::getCurrentHIPStream().stream());
 }
 
 void bn_fwd_apply(torch::Tensor x, torch::Tensor res, torch::Tensor y,
@@ -496,6 +519,84 @@ void maxpool3x3s2_bwd(torch::Tensor dy, torch::Tensor code,
                      at::cuda::getCurrentHIPStream().stream());
 }
 
+// Stem backward with the un-pool fused into the recompute-mask BN passes
+// (fused_bn.hip): dp is the pooled grad [N,C,Ho,Wo], code the forward's
+// u8 argmax codes, x the conv output [N,C,H,W]; the un-pooled map is
+// rebuilt in registers and never stored. Returns the tile geometry after
+// the shape checks both entry points share.
+struct _PoolGeom { int N, C, H, W, Ho, Wo; };
+
+static _PoolGeom _check_bn_pool_bwd(const torch::Tensor& dp,
+                                    const torch::Tensor& code,
+                                    const torch::Tensor& x) {
+  _check_bn_act(dp, "dp"); _check_bn_act(x, "x");
+  TORCH_CHECK(code.scalar_type() == torch::kUInt8 && code.is_cuda() &&
+                  code.is_contiguous(),
+              "code must be contiguous u8 on GPU");
+  TORCH_CHECK(x.dim() == 4 && dp.dim() == 4, "x and dp must be 4-d");
+  TORCH_CHECK(x.is_contiguous(at::MemoryFormat::ChannelsLast) &&
+                  dp.is_contiguous(at::MemoryFormat::ChannelsLast),
+              "x and dp must be channels_last");
+  _PoolGeom g{(int)x.size(0), (int)x.size(1), (int)x.size(2),
+              (int)x.size(3), (int)dp.size(2), (int)dp.size(3)};
+  TORCH_CHECK(g.C % 8 == 0 && 256 % (g.C / 8) == 0, "bad C");
+  TORCH_CHECK(dp.size(0) == g.N && dp.size(1) == g.C, "dp N/C mismatch");
+  TORCH_CHECK(g.Ho == (g.H + 1) / 2 && g.Wo == (g.W + 1) / 2,
+              "3x3 s2 p1 shape");
+  TORCH_CHECK(code.numel() == dp.numel(), "code/dp size mismatch");
+  // the kernels decompose the tile index in 32 bits
+  TORCH_CHECK((int64_t)g.N * g.Ho * g.Wo < (int64_t(1) << 31),
+              "N*Ho*Wo must be < 2^31");
+  return g;
+}
+
+torch::Tensor bn_pool_bwd_reduce(torch::Tensor dp, torch::Tensor code,
+                                 torch::Tensor x, torch::Tensor mean,
+                                 torch::Tensor invstd, torch::Tensor weight,
+                                 torch::Tensor bias) {
+  _PoolGeom g = _check_bn_pool_bwd(dp, code, x);
+  _check_f32(mean, "mean"); _check_f32(invstd, "invstd");
+  _check_f32(weight, "weight"); _check_f32(bias, "bias");
+  TORCH_CHECK(mean.numel() == g.C && invstd.numel() == g.C &&
+                  weight.numel() == g.C && bias.numel() == g.C,
+              "channel vectors must be [C]");
+  int nb = bn_reduce_blocks((long long)g.N * g.Ho * g.Wo, g.C);
+  auto partial = torch::empty(
+      {(int64_t)nb * 2 * g.C},
+      torch::TensorOptions().dtype(torch::kFloat32).device(x.device()));
+  launch_bn_pool_bwd_reduce(dp.data_ptr(), code.data_ptr<uint8_t>(),
+                            x.data_ptr(), mean.data_ptr<float>(),
+                            invstd.data_ptr<float>(),
+                            weight.data_ptr<float>(),
+                            bias.data_ptr<float>(),
+                            partial.data_ptr<float>(), nb, g.N, g.H, g.W,
+                            g.Ho, g.Wo, g.C,
+                            at::cuda::getCurrentHIPStream().stream());
+  return partial;
+}
+
+void bn_pool_bwd_apply(torch::Tensor dp, torch::Tensor code, torch::Tensor x,
+                       torch::Tensor mean, torch::Tensor invstd,
+                       torch::Tensor bias, torch::Tensor k,
+                       torch::Tensor dx) {
+  _PoolGeom g = _check_bn_pool_bwd(dp, code, x);
+  _check_bn_act(dx, "dx");
+  _check_f32(mean, "mean"); _check_f32(invstd, "invstd");
+  _check_f32(bias, "bias"); _check_f32(k, "k");
+  TORCH_CHECK(mean.numel() == g.C && invstd.numel() == g.C &&
+                  bias.numel() == g.C && k.numel() == 3 * g.C,
+              "channel vectors must be [C], k [3C]");
+  TORCH_CHECK(dx.sizes() == x.sizes() &&
+                  dx.is_contiguous(at::MemoryFormat::ChannelsLast),
+              "dx must match x (channels_last)");
+  launch_bn_pool_bwd_apply(dp.data_ptr(), code.data_ptr<uint8_t>(),
+                           x.data_ptr(), mean.data_ptr<float>(),
+                           invstd.data_ptr<float>(), bias.data_ptr<float>(),
+                           k.data_ptr<float>(), dx.data_ptr(), g.N, g.H,
+                           g.W, g.Ho, g.Wo, g.C,
+                           at::cuda::getCurrentHIPStream().stream());
+}
+
 // ---------------------------------------------------------------- flat Adam
 extern "C" void launch_adam_step(float* p, const float* g, float* m,
                                  float* v, int* step, float lr, float beta1,
@@ -653,7 +754,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("exog_project_mfma", &exog_project_mfma,
         "design-matrix GEMM beta = P @ Wc on f32 MFMA");
   m.def("bn_fwd_reduce", &bn_fwd_reduce);
-  m.def("bn_fwd_finalize", &bn_fwd_finalize);
+  m.def("bn_fwd_finalize", &bn_fwd_finalize,
+        "mean/invstd + running stats (+ optional int64 step counter)",
+        pybind11::arg("partial"), pybind11::arg("mean"),
+        pybind11::arg("invstd"), pybind11::arg("running_mean"),
+        pybind11::arg("running_var"), pybind11::arg("momentum"),
+        pybind11::arg("eps"), pybind11::arg("rows"), pybind11::arg("C"),
+        pybind11::arg("update_running"),
+        pybind11::arg("num_batches_tracked") = pybind11::none());
   m.def("bn_fwd_apply", &bn_fwd_apply);
   m.def("bn_bwd_reduce", &bn_bwd_reduce);
   m.def("bn_bwd_reduce_rm", &bn_bwd_reduce_rm);
@@ -666,6 +774,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("maxpool3x3s2_fwd", &maxpool3x3s2_fwd);
   m.def("bn_maxpool3x3s2_fwd", &bn_maxpool3x3s2_fwd);
   m.def("maxpool3x3s2_bwd", &maxpool3x3s2_bwd);
+  m.def("bn_pool_bwd_reduce", &bn_pool_bwd_reduce,
+        "stem BN bwd reduce with the max-unpool rebuilt in registers");
+  m.def("bn_pool_bwd_apply", &bn_pool_bwd_apply,
+        "stem BN bwd apply with the max-unpool rebuilt in registers");
   m.def("adam_step_mixed", &adam_step_mixed,
         "fused flat Adam with bf16 params/grads + fp32 master");
   m.def("arma_generate", &arma_generate,

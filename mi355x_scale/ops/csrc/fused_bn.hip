@@ -27,8 +27,16 @@
 //   * block-level partials are tree-reduced through LDS (16 KB of the
 //     160 KB/CU) and committed with fp32 global atomics (C <= 512 means
 //     contention is negligible).
-// All six kernels are stream-ordered device work with no host sync, so
+// All kernels are stream-ordered device work with no host sync, so
 // the whole fused op captures into hipGraphs (train/graphstep.py).
+//
+// Later additions, described at their definitions below:
+//   * recompute-mask backward (bn_bwd_*_rm): the relu mask comes from
+//     (w*xhat + b) > 0, so the stored y is not read;
+//   * stem backward (bn_pool_bwd_*): the max-unpool of the pooled
+//     gradient is rebuilt in registers inside both passes, so the
+//     un-pooled map is never written or read;
+//   * bn_fwd_finalize also bumps the module's num_batches_tracked.
 //
 // Reference parity: this implements the BatchNorm2d semantics the
 // reference's torchvision resnet50 relies on
@@ -119,12 +127,15 @@ __global__ __launch_bounds__(256) void bn_fwd_reduce_kernel(
 // run (coalesced), then an in-wavefront shuffle tree. mean/invstd out +
 // momentum update of running stats (unbiased running var, matching torch
 // BatchNorm2d). Device-side so it replays inside hipGraphs; fixed
-// summation order = deterministic.
+// summation order = deterministic. When num_batches_tracked is non-null
+// the channel-0 lane-0 thread also bumps the module's int64 step counter,
+// so the training forward needs no separate `+= 1` elementwise kernel.
 __global__ __launch_bounds__(256) void bn_fwd_finalize_kernel(
     const float* __restrict__ partial, int nblocks,
     float* __restrict__ mean, float* __restrict__ invstd,
     float* __restrict__ running_mean, float* __restrict__ running_var,
-    float momentum, float eps, long long rows, int C, int update_running) {
+    float momentum, float eps, long long rows, int C, int update_running,
+    long long* __restrict__ num_batches_tracked) {
   int c = blockIdx.x * (blockDim.x / 64) + threadIdx.x / 64;
   int lane = threadIdx.x % 64;
   if (c >= C) return;
@@ -149,6 +160,7 @@ __global__ __launch_bounds__(256) void bn_fwd_finalize_kernel(
     running_mean[c] = (1.f - momentum) * running_mean[c] + momentum * m;
     running_var[c] = (1.f - momentum) * running_var[c] + momentum * unbiased;
   }
+  if (c == 0 && num_batches_tracked) *num_batches_tracked += 1;
 }
 
 // ---------------------------------------------------------------- fwd apply
@@ -396,6 +408,31 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(
 // recompute is if anything closer to the fp32 reference than masking on
 // the rounded bf16 y. Residual layers keep the y path (the mask there
 // depends on the residual input).
+//
+// The per-element arithmetic of the recompute-mask path lives in the three
+// helpers below, with its fused multiply-adds spelled out. The row-order
+// rm kernels and the stem's tile-order bn_pool_bwd_* kernels all call
+// them, so the two paths round identically by construction, whatever the
+// compiler's contraction choices are for either loop shape.
+static __device__ __forceinline__ float rm_masked_dy(float dy, float w,
+                                                     float xhat, float b) {
+  if (fmaf(w, xhat, b) <= 0.f) dy = 0.f;
+  return dy;
+}
+
+static __device__ __forceinline__ void rm_accumulate(float dy, float xhat,
+                                                     float& sdy,
+                                                     float& sdyx) {
+  sdy += dy;
+  sdyx = fmaf(dy, xhat, sdyx);
+}
+
+// dx = w*invstd * (dy - mean_dy - xhat*mean_dy_xhat)
+static __device__ __forceinline__ float rm_dx(float wis, float dy, float k1,
+                                              float xhat, float k2) {
+  return wis * fmaf(-xhat, k2, dy - k1);
+}
+
 template <bool WRITE_DY>
 __global__ __launch_bounds__(256) void bn_bwd_reduce_rm_kernel(
     const bf16* __restrict__ dz, const bf16* __restrict__ x,
@@ -429,10 +466,8 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_rm_kernel(
 #pragma unroll
     for (int j = 0; j < VEC; ++j) {
       float xhat = (__bfloat162float(xv.h[j]) - m[j]) * is[j];
-      float dy = __bfloat162float(g.h[j]);
-      if (wv[j] * xhat + bv[j] <= 0.f) dy = 0.f;
-      sdy[j] += dy;
-      sdyx[j] += dy * xhat;
+      float dy = rm_masked_dy(__bfloat162float(g.h[j]), wv[j], xhat, bv[j]);
+      rm_accumulate(dy, xhat, sdy[j], sdyx[j]);
       if (WRITE_DY) dyv.h[j] = __float2bfloat16(dy);
     }
     if (WRITE_DY) store8(dym + off, dyv);
@@ -497,12 +532,231 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_rm_kernel(
 #pragma unroll
     for (int j = 0; j < VEC; ++j) {
       float xhat = (__bfloat162float(xv.h[j]) - m[j]) * is[j];
-      float dy = __bfloat162float(g.h[j]);
-      if (wv[j] * xhat + bv[j] <= 0.f) dy = 0.f;
-      float v = wis[j] * (dy - k1[j] - xhat * k2[j]);
+      float dy = rm_masked_dy(__bfloat162float(g.h[j]), wv[j], xhat, bv[j]);
+      float v = rm_dx(wis[j], dy, k1[j], xhat, k2[j]);
       odx.h[j] = __float2bfloat16(v);
     }
     store8(dx + off, odx);
+  }
+}
+
+// ------------------------------------------------- stem bwd, un-pool fused
+// The stem's backward used to run maxpool3x3s2_bwd -> reduce_rm -> apply_rm:
+// the un-pooled gradient map dz (same size as x, 340 MB at bs 212) was
+// written once and read twice, although it is only a sparse scatter of
+// the pooled grad dp selected by the u8 window code. The two kernels
+// below rebuild the tile's four dz values in registers instead, so dz is
+// never materialized.
+//
+// Mapping is maxpool_bwd_kernel's (maxpool.hip): one thread-lane owns the
+// 2x2 input tile at (2i, 2j) for 8 channels; tiles == the pooled grid.
+// Each of the tile's pixels sits at a fixed position inside the (up to)
+// four windows that touch it, so every dp/code vector is loaded once and
+// all code compares are against constants. Each un-pooled value is
+// rounded to bf16 and widened again so it equals what maxpool_bwd_kernel
+// would have stored. (The tile code is repeated here rather than shared
+// through a header: a local header makes the extension build emit
+// hipified copies of both .hip files into the source tree.)
+union CVec {
+  uint2 u;
+  unsigned char c[VEC];
+};
+
+// Tile decomposition shared by both passes. pix[p] is the NHWC element
+// offset of tile pixel p (0:(2i,2j) 1:(2i,2j+1) 2:(2i+1,2j) 3:(2i+1,2j+1)),
+// valid[p] its in-image guard for odd H / W.
+struct PoolTile {
+  float a[4][VEC];
+  long long pix[4];
+  bool valid[4];
+};
+
+static __device__ __forceinline__ void unpool_tile(
+    const bf16* __restrict__ dp, const unsigned char* __restrict__ code,
+    int r32, int lane, int H, int W, int Ho, int Wo, int C, PoolTile& t) {
+  const int j = r32 % Wo;
+  const int t32 = r32 / Wo;
+  const int i = t32 % Ho;
+  const int n = t32 / Ho;
+  const long long lvec = (long long)lane * VEC;
+
+  BVec g00{}, g01{}, g10{}, g11{};
+  CVec c00{}, c01{}, c10{}, c11{};
+  const bool v01 = (j + 1 < Wo), v10 = (i + 1 < Ho);
+  const long long base = (((long long)n * Ho + i) * Wo + j) * C + lvec;
+  g00.u = *reinterpret_cast<const uint4*>(dp + base);
+  c00.u = *reinterpret_cast<const uint2*>(code + base);
+  if (v01) {
+    g01.u = *reinterpret_cast<const uint4*>(dp + base + C);
+    c01.u = *reinterpret_cast<const uint2*>(code + base + C);
+  }
+  if (v10) {
+    const long long b2 = base + (long long)Wo * C;
+    g10.u = *reinterpret_cast<const uint4*>(dp + b2);
+    c10.u = *reinterpret_cast<const uint2*>(code + b2);
+    if (v01) {
+      g11.u = *reinterpret_cast<const uint4*>(dp + b2 + C);
+      c11.u = *reinterpret_cast<const uint2*>(code + b2 + C);
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < VEC; ++k) {
+    float a00 = (c00.c[k] == 4) ? __bfloat162float(g00.h[k]) : 0.f;
+    float a01 = (c00.c[k] == 5) ? __bfloat162float(g00.h[k]) : 0.f;
+    if (v01 && c01.c[k] == 3) a01 += __bfloat162float(g01.h[k]);
+    float a10 = (c00.c[k] == 7) ? __bfloat162float(g00.h[k]) : 0.f;
+    if (v10 && c10.c[k] == 1) a10 += __bfloat162float(g10.h[k]);
+    float a11 = (c00.c[k] == 8) ? __bfloat162float(g00.h[k]) : 0.f;
+    if (v01 && c01.c[k] == 6) a11 += __bfloat162float(g01.h[k]);
+    if (v10 && c10.c[k] == 2) a11 += __bfloat162float(g10.h[k]);
+    if (v10 && v01 && c11.c[k] == 0) a11 += __bfloat162float(g11.h[k]);
+    t.a[0][k] = __bfloat162float(__float2bfloat16(a00));
+    t.a[1][k] = __bfloat162float(__float2bfloat16(a01));
+    t.a[2][k] = __bfloat162float(__float2bfloat16(a10));
+    t.a[3][k] = __bfloat162float(__float2bfloat16(a11));
+  }
+  const int h0 = 2 * i, w0 = 2 * j;
+  const bool r1 = (h0 + 1 < H), cL1 = (w0 + 1 < W);
+  const long long ibase = (((long long)n * H + h0) * W + w0) * C + lvec;
+  t.pix[0] = ibase;
+  t.pix[1] = ibase + C;
+  t.pix[2] = ibase + (long long)W * C;
+  t.pix[3] = ibase + (long long)W * C + C;
+  t.valid[0] = true;
+  t.valid[1] = cL1;
+  t.valid[2] = r1;
+  t.valid[3] = r1 && cL1;
+}
+
+// Same math, LDS tree and [2C][nblocks] partial layout as
+// bn_bwd_reduce_rm_kernel<false>, so bn_bwd_finalize is reused unchanged;
+// only the fp32 summation order differs (tile order, not row order).
+//
+// Per-element math goes through the rm_* helpers shared with the rm
+// kernels (explicit fmaf): here the per-pixel edge guards split the loop
+// body into basic blocks, and left to the compiler, contraction would not
+// cross them and some pixels would round differently from the unfused
+// path.
+__global__ __launch_bounds__(256) void bn_pool_bwd_reduce_kernel(
+    const bf16* __restrict__ dp, const unsigned char* __restrict__ code,
+    const bf16* __restrict__ x, const float* __restrict__ mean,
+    const float* __restrict__ invstd, const float* __restrict__ weight,
+    const float* __restrict__ bias, float* __restrict__ partial, int N,
+    int H, int W, int Ho, int Wo, int C) {
+  const int lanes = C / VEC;
+  const int lane = threadIdx.x % lanes;
+  const int rsub = threadIdx.x / lanes;
+  const int rows_per_iter = blockDim.x / lanes;
+  const long long tiles = (long long)N * Ho * Wo;
+  const long long rstride = (long long)gridDim.x * rows_per_iter;
+
+  float m[VEC], is[VEC], wv[VEC], bv[VEC];
+#pragma unroll
+  for (int j = 0; j < VEC; ++j) {
+    int c = lane * VEC + j;
+    m[j] = mean[c];
+    is[j] = invstd[c];
+    wv[j] = weight[c];
+    bv[j] = bias[c];
+  }
+
+  float sdy[VEC] = {0.f}, sdyx[VEC] = {0.f};
+  for (long long row = (long long)blockIdx.x * rows_per_iter + rsub;
+       row < tiles; row += rstride) {
+    PoolTile t;
+    unpool_tile(dp, code, (int)row, lane, H, W, Ho, Wo, C, t);
+    BVec xv[4];
+#pragma unroll
+    for (int p = 0; p < 4; ++p)
+      if (t.valid[p]) xv[p] = load8(x + t.pix[p]);
+#pragma unroll
+    for (int p = 0; p < 4; ++p) {
+      if (!t.valid[p]) continue;
+#pragma unroll
+      for (int j = 0; j < VEC; ++j) {
+        float xhat = (__bfloat162float(xv[p].h[j]) - m[j]) * is[j];
+        float dy = rm_masked_dy(t.a[p][j], wv[j], xhat, bv[j]);
+        rm_accumulate(dy, xhat, sdy[j], sdyx[j]);
+      }
+    }
+  }
+
+  __shared__ float lds[256 * 2 * VEC];
+  float* mys = &lds[(rsub * lanes + lane) * 2 * VEC];
+#pragma unroll
+  for (int j = 0; j < VEC; ++j) {
+    mys[j] = sdy[j];
+    mys[VEC + j] = sdyx[j];
+  }
+  __syncthreads();
+  for (int step = rows_per_iter >> 1; step > 0; step >>= 1) {
+    if (rsub < step) {
+      const float* other = &lds[((rsub + step) * lanes + lane) * 2 * VEC];
+#pragma unroll
+      for (int j = 0; j < 2 * VEC; ++j) mys[j] += other[j];
+    }
+    __syncthreads();
+  }
+  if (rsub == 0) {
+#pragma unroll
+    for (int j = 0; j < VEC; ++j) {
+      partial[(long long)(lane * VEC + j) * gridDim.x + blockIdx.x] = mys[j];
+      partial[(long long)(C + lane * VEC + j) * gridDim.x + blockIdx.x] =
+          mys[VEC + j];
+    }
+  }
+}
+
+// Arithmetic is bn_bwd_apply_rm_kernel's (the shared rm_* helpers, and
+// wv = wis / is), so given the same k the dx map is bit-identical to the
+// unfused path.
+__global__ __launch_bounds__(256) void bn_pool_bwd_apply_kernel(
+    const bf16* __restrict__ dp, const unsigned char* __restrict__ code,
+    const bf16* __restrict__ x, const float* __restrict__ mean,
+    const float* __restrict__ invstd, const float* __restrict__ bias,
+    const float* __restrict__ k, bf16* __restrict__ dx, int N, int H, int W,
+    int Ho, int Wo, int C) {
+  const int lanes = C / VEC;
+  const int lane = threadIdx.x % lanes;
+  const int rsub = threadIdx.x / lanes;
+  const int rows_per_iter = blockDim.x / lanes;
+  const long long tiles = (long long)N * Ho * Wo;
+  const long long rstride = (long long)gridDim.x * rows_per_iter;
+
+  float m[VEC], is[VEC], wis[VEC], k1[VEC], k2[VEC], bv[VEC], wv[VEC];
+#pragma unroll
+  for (int j = 0; j < VEC; ++j) {
+    int c = lane * VEC + j;
+    m[j] = mean[c];
+    is[j] = invstd[c];
+    wis[j] = k[c];          // w * invstd
+    k1[j] = k[C + c];
+    k2[j] = k[2 * C + c];
+    bv[j] = bias[c];
+    wv[j] = wis[j] / is[j];  // w, recovered once per channel
+  }
+
+  for (long long row = (long long)blockIdx.x * rows_per_iter + rsub;
+       row < tiles; row += rstride) {
+    PoolTile t;
+    unpool_tile(dp, code, (int)row, lane, H, W, Ho, Wo, C, t);
+    BVec xv[4];
+#pragma unroll
+    for (int p = 0; p < 4; ++p)
+      if (t.valid[p]) xv[p] = load8(x + t.pix[p]);
+#pragma unroll
+    for (int p = 0; p < 4; ++p) {
+      if (!t.valid[p]) continue;
+      BVec odx;
+#pragma unroll
+      for (int j = 0; j < VEC; ++j) {
+        float xhat = (__bfloat162float(xv[p].h[j]) - m[j]) * is[j];
+        float dy = rm_masked_dy(t.a[p][j], wv[j], xhat, bv[j]);
+        float v = rm_dx(wis[j], dy, k1[j], xhat, k2[j]);
+        odx.h[j] = __float2bfloat16(v);
+      }
+      store8(dx + t.pix[p], odx);
+    }
   }
 }
 
@@ -539,12 +793,13 @@ extern "C" void launch_bn_fwd_finalize(const float* partial, int nblocks,
                                        float* running_var, float momentum,
                                        float eps, long long rows, int C,
                                        int update_running,
+                                       long long* num_batches_tracked,
                                        hipStream_t stream) {
   // 4 wavefronts (= 4 channels) per block
   hipLaunchKernelGGL(bn_fwd_finalize_kernel, dim3((C + 3) / 4),
                      dim3(256), 0, stream, partial, nblocks, mean, invstd,
                      running_mean, running_var, momentum, eps, rows, C,
-                     update_running);
+                     update_running, num_batches_tracked);
 }
 
 extern "C" void launch_bn_fwd_apply(const void* x, const void* res, void* y,
@@ -610,6 +865,29 @@ extern "C" void launch_bn_bwd_apply_rm(const void* dz, const void* x,
                      dim3(256), 0, stream, (const bf16*)dz,
                      (const bf16*)x, mean, invstd, bias, k, (bf16*)dx,
                      rows, C);
+}
+
+// Stem pair: the grids are sized over the tile count N*Ho*Wo (the caller
+// passes nblocks = bn_reduce_blocks(tiles, C) for the reduce).
+extern "C" void launch_bn_pool_bwd_reduce(
+    const void* dp, const unsigned char* code, const void* x,
+    const float* mean, const float* invstd, const float* weight,
+    const float* bias, float* partial, int nblocks, int N, int H, int W,
+    int Ho, int Wo, int C, hipStream_t stream) {
+  hipLaunchKernelGGL(bn_pool_bwd_reduce_kernel, dim3(nblocks), dim3(256), 0,
+                     stream, (const bf16*)dp, code, (const bf16*)x, mean,
+                     invstd, weight, bias, partial, N, H, W, Ho, Wo, C);
+}
+
+extern "C" void launch_bn_pool_bwd_apply(
+    const void* dp, const unsigned char* code, const void* x,
+    const float* mean, const float* invstd, const float* bias,
+    const float* k, void* dx, int N, int H, int W, int Ho, int Wo, int C,
+    hipStream_t stream) {
+  hipLaunchKernelGGL(bn_pool_bwd_apply_kernel,
+                     dim3(pick_grid((long long)N * Ho * Wo, C)), dim3(256),
+                     0, stream, (const bf16*)dp, code, (const bf16*)x, mean,
+                     invstd, bias, k, (bf16*)dx, N, H, W, Ho, Wo, C);
 }
 
 extern "C" void launch_bn_bwd_apply_dym(const void* dym, const void* x,

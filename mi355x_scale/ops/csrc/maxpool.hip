@@ -12,6 +12,12 @@
 //     matches (torch's NHWC backward scatters with atomics).
 // Both kernels use the BN-style mapping: consecutive threads cover
 // consecutive 8-channel slots, vectorized 16 B loads/stores.
+//
+// The flagship's stem no longer launches maxpool_bwd_kernel: its 2x2
+// tile un-pool is repeated in registers by bn_pool_bwd_reduce/apply
+// (fused_bn.hip), which must keep producing exactly the values this
+// kernel stores. It stays the standalone MaxPool backward and the
+// reference the fused pair is tested against.
 
 #include <hip/hip_runtime.h>
 #include <hip/hip_bf16.h>

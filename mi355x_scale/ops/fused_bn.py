@@ -20,6 +20,13 @@ stored y is read by NEITHER backward pass and is not saved; and the
 stem's ``forward_pooled`` folds the affine+relu into the maxpool window
 reads so the normalized stem map is never materialized at all.
 
+Round 3: the stem backward no longer materializes the un-pooled gradient
+map either — ``bn_pool_bwd_reduce`` / ``bn_pool_bwd_apply`` rebuild it in
+registers from the pooled grad and the u8 window codes
+(``MI355X_BN_POOL_FUSED_BWD=0`` selects the three-kernel path for A/B);
+and on the HIP training path ``bn_fwd_finalize`` bumps
+``num_batches_tracked`` on the device, so no per-BN ``+= 1`` kernel runs.
+
 All device work is stream-ordered with no host sync, so the op captures
 into hipGraphs (train/graphstep.py).
 """
@@ -46,15 +53,16 @@ def _hip_supported(x: torch.Tensor) -> bool:
 class _FusedBNFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, residual, weight, bias, running_mean, running_var,
-                momentum, eps, relu):
+                momentum, eps, relu, num_batches_tracked):
         C = x.shape[1]
         rows = x.numel() // C
         dev = x.device
         mean = torch.empty(C, dtype=torch.float32, device=dev)
         invstd = torch.empty(C, dtype=torch.float32, device=dev)
         partial = _C.bn_fwd_reduce(x, C)
+        # the finalize kernel also bumps the step counter when given one
         _C.bn_fwd_finalize(partial, mean, invstd, running_mean, running_var,
-                           momentum, eps, rows, C, True)
+                           momentum, eps, rows, C, True, num_batches_tracked)
         y = torch.empty_like(x)
         res = residual if residual is not None else x.new_empty(0)
         _C.bn_fwd_apply(x, res, y, mean, invstd, weight, bias, C, relu)
@@ -114,7 +122,7 @@ class _FusedBNFn(torch.autograd.Function):
             _C.bn_bwd_apply_dym(dym, x, mean, invstd, k, dx, C)
             return (dx, dym, None if fuse_acc else dweight,
                     None if fuse_acc else dbias, None, None, None, None,
-                    None)
+                    None, None)
         if ctx.relu:
             # recompute-mask path: one full activation-map read (the
             # stored y) drops out of BOTH backward passes
@@ -131,7 +139,8 @@ class _FusedBNFn(torch.autograd.Function):
             _C.bn_bwd_apply(dz, y, x, mean, invstd, k, dx, x.new_empty(0),
                             C, False)
         return (dx, None, None if fuse_acc else dweight,
-                None if fuse_acc else dbias, None, None, None, None, None)
+                None if fuse_acc else dbias, None, None, None, None, None,
+                None)
 
 
 class _FusedBNPoolFn(torch.autograd.Function):
@@ -141,7 +150,7 @@ class _FusedBNPoolFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, weight, bias, running_mean, running_var,
-                momentum, eps, training):
+                momentum, eps, training, num_batches_tracked):
         C = x.shape[1]
         dev = x.device
         if training:
@@ -149,8 +158,10 @@ class _FusedBNPoolFn(torch.autograd.Function):
             mean = torch.empty(C, dtype=torch.float32, device=dev)
             invstd = torch.empty(C, dtype=torch.float32, device=dev)
             partial = _C.bn_fwd_reduce(x, C)
+            # the finalize kernel also bumps the step counter
             _C.bn_fwd_finalize(partial, mean, invstd, running_mean,
-                               running_var, momentum, eps, rows, C, True)
+                               running_var, momentum, eps, rows, C, True,
+                               num_batches_tracked)
         else:
             mean = running_mean.to(torch.float32)
             invstd = torch.rsqrt(running_var.to(torch.float32) + eps)
@@ -171,10 +182,15 @@ class _FusedBNPoolFn(torch.autograd.Function):
         dev = x.device
         if not dp.is_contiguous(memory_format=torch.channels_last):
             dp = dp.contiguous(memory_format=torch.channels_last)
-        # un-pool: scatter the pooled grad to the argmax positions
-        dz = torch.empty_like(x)
-        _C.maxpool3x3s2_bwd(dp, code, dz)
-        # then the recompute-mask BN backward (fused_bn.hip rm kernels)
+        import os
+        # Default: the un-pooled map dz is rebuilt in registers inside
+        # both BN passes (bn_pool_bwd_* kernels) and never allocated.
+        # MI355X_BN_POOL_FUSED_BWD=0 selects the three-kernel path
+        # (un-pool to dz, then the rm kernels) for A/B runs and tests.
+        # Deliberately no hasattr() probe for the new pair: the extension
+        # is built from this tree, and an extension without them must
+        # raise rather than quietly run the slower path.
+        fused_unpool = os.environ.get("MI355X_BN_POOL_FUSED_BWD", "1") != "0"
         k = torch.empty(3 * C, dtype=torch.float32, device=dev)
 
         def _grad_view(p):
@@ -184,7 +200,6 @@ class _FusedBNPoolFn(torch.autograd.Function):
                 return g
             return None
 
-        import os
         wg, bg = _grad_view(weight), _grad_view(bias)
         fuse_acc = (torch.cuda.is_current_stream_capturing()
                     and wg is not None and bg is not None
@@ -195,13 +210,25 @@ class _FusedBNPoolFn(torch.autograd.Function):
             dweight = torch.empty(C, dtype=torch.float32, device=dev)
             dbias = torch.empty(C, dtype=torch.float32, device=dev)
         dx = torch.empty_like(x)
-        partial = _C.bn_bwd_reduce_rm(dz, x, mean, invstd, weight, bias,
-                                      x.new_empty(0), C)
-        _C.bn_bwd_finalize(partial, invstd, weight, dweight, dbias, k,
-                           rows, C, fuse_acc)
-        _C.bn_bwd_apply_rm(dz, x, mean, invstd, bias, k, dx, C)
+        if fused_unpool:
+            partial = _C.bn_pool_bwd_reduce(dp, code, x, mean, invstd,
+                                            weight, bias)
+            _C.bn_bwd_finalize(partial, invstd, weight, dweight, dbias, k,
+                               rows, C, fuse_acc)
+            _C.bn_pool_bwd_apply(dp, code, x, mean, invstd, bias, k, dx)
+        else:
+            # un-pool: scatter the pooled grad to the argmax positions,
+            # then the recompute-mask BN backward (fused_bn.hip rm kernels)
+            dz = torch.empty_like(x)
+            _C.maxpool3x3s2_bwd(dp, code, dz)
+            partial = _C.bn_bwd_reduce_rm(dz, x, mean, invstd, weight, bias,
+                                          x.new_empty(0), C)
+            _C.bn_bwd_finalize(partial, invstd, weight, dweight, dbias, k,
+                               rows, C, fuse_acc)
+            _C.bn_bwd_apply_rm(dz, x, mean, invstd, bias, k, dx, C)
         return (dx, None if fuse_acc else dweight,
-                None if fuse_acc else dbias, None, None, None, None, None)
+                None if fuse_acc else dbias, None, None, None, None, None,
+                None)
 
 
 class FusedBNReLU2d(nn.Module):
@@ -241,18 +268,17 @@ class FusedBNReLU2d(nn.Module):
         assert self.relu, "pooled fusion is relu-only"
         if _hip_supported(x):
             require_ext()
-            if self.training:
-                self.num_batches_tracked += 1
+            # training: bn_fwd_finalize bumps num_batches_tracked on the
+            # device (no separate `+= 1` kernel); eval leaves it alone
             x = x.contiguous(memory_format=torch.channels_last)
             return _FusedBNPoolFn.apply(
                 x, self.weight, self.bias, self.running_mean,
-                self.running_var, self.momentum, self.eps, self.training)
+                self.running_var, self.momentum, self.eps, self.training,
+                self.num_batches_tracked)
         return F.max_pool2d(self.forward(x), 3, stride=2, padding=1)
 
     def forward(self, x: torch.Tensor,
                 residual: Optional[torch.Tensor] = None) -> torch.Tensor:
-        if self.training:
-            self.num_batches_tracked += 1
         if _hip_supported(x):
             require_ext()  # GPU bf16 path never falls back silently
             x = x.contiguous(memory_format=torch.channels_last)
@@ -260,9 +286,11 @@ class FusedBNReLU2d(nn.Module):
                 residual = residual.contiguous(
                     memory_format=torch.channels_last)
             if self.training:
+                # bn_fwd_finalize bumps num_batches_tracked on the device
                 return _FusedBNFn.apply(
                     x, residual, self.weight, self.bias, self.running_mean,
-                    self.running_var, self.momentum, self.eps, self.relu)
+                    self.running_var, self.momentum, self.eps, self.relu,
+                    self.num_batches_tracked)
             if not (torch.is_grad_enabled() and
                     (x.requires_grad or self.weight.requires_grad)):
                 # inference: apply-only with running stats
@@ -274,6 +302,8 @@ class FusedBNReLU2d(nn.Module):
                                 self.relu)
                 return y
         # reference composition (CPU path and numerics oracle)
+        if self.training:
+            self.num_batches_tracked += 1
         if x.is_cuda and len(FusedBNReLU2d.gpu_fallbacks) < 256:
             # bounded: diagnostic only (tests assert it stays empty on
             # the flagship path)
