@@ -59,6 +59,39 @@ def main():
         out2.backward(dy, retain_graph=True)
     t_wrw = timeit(mfma_wrw)
 
+    # --- forward phase split, both kernels: phase_mask 1 = band staging
+    # only, 4 = MFMA + epilogue only (on an unstaged band), 7 = all.
+    # "rows1" is the one-row-per-block kernel, "fused" the multi-row
+    # kernel with wide stores and BN partial sums (pad-weights launch
+    # included in every figure, ~2 us).
+    from mi355x_scale.ops import _C
+    ho, wo = (h - 1) // 2 + 1, (w - 1) // 2 + 1
+    o_nhwc = torch.empty(n, ho, wo, 64, dtype=torch.bfloat16, device=dev)
+    wp = torch.empty(64 * 160, dtype=torch.bfloat16, device=dev)
+    part = torch.empty(2 * 64 * _C.stem_fwd_blocks(n, ho),
+                       dtype=torch.float32, device=dev)
+    xn, wn = x.permute(0, 2, 3, 1), wt.permute(0, 2, 3, 1)
+    phases = {}
+    for name, p in (("rows1", None), ("fused", part)):
+        phases[name] = {
+            label: round(timeit(
+                lambda: _C.stem_conv_fwd(xn, wn, o_nhwc, wp, mask, p)), 1)
+            for label, mask in (("stage", 1), ("mfma_store", 4), ("all", 7))}
+    # what the BN statistics of the stem map cost on top of each
+    out_cl = _StemConvFn.apply(x, wt)
+    mean = torch.empty(64, dtype=torch.float32, device=dev)
+    invstd = torch.empty(64, dtype=torch.float32, device=dev)
+    rm, rv = torch.zeros(64, device=dev), torch.ones(64, device=dev)
+    rows = n * ho * wo
+
+    def stats_separate():
+        _C.bn_fwd_finalize(_C.bn_fwd_reduce(out_cl, 64), mean, invstd, rm,
+                           rv, 0.1, 1e-5, rows, 64, True)
+    t_stats_sep = timeit(stats_separate)
+    _C.stem_conv_fwd(xn, wn, o_nhwc, wp, 7, part)
+    t_stats_fin = timeit(lambda: _C.bn_fwd_finalize(
+        part, mean, invstd, rm, rv, 0.1, 1e-5, rows, 64, True))
+
     # numerics cross-check at this exact shape
     ref = F.conv2d(x.float(), wt.float(), None, 2, 3)
     got = _StemConvFn.apply(x, wt).float()
@@ -70,6 +103,10 @@ def main():
                    "speedup": round(t_mio_fwd / t_fwd, 2)},
         "wrw_us": {"miopen": round(t_mio_wrw, 1), "mfma": round(t_wrw, 1),
                    "speedup": round(t_mio_wrw / t_wrw, 2)},
+        "fwd_phase_us": phases,
+        "stem_bn_stats_us": {"reduce+finalize": round(t_stats_sep, 1),
+                             "finalize_on_conv_partial":
+                                 round(t_stats_fin, 1)},
         "fwd_rel_err_vs_fp32": round(rel, 5),
     }))
 

@@ -120,7 +120,14 @@ class ResNet(nn.Module):
         # stem: bn1's relu+affine fold INTO the pool window reads (the
         # normalized map is never materialized — ops/fused_bn.py
         # forward_pooled); composed ops off the GPU bf16 path
-        x = self.bn1.forward_pooled(self.conv1(x))
+        if self.bn1.training and self.conv1.stats_ok(x):
+            # the conv's epilogue already summed bn1's batch statistics:
+            # no second read of the stem map (MI355X_STEM_FUSED_STATS=0
+            # takes the branch below)
+            x, partial = self.conv1.forward_with_stats(x)
+            x = self.bn1.forward_pooled(x, partial)
+        else:
+            x = self.bn1.forward_pooled(self.conv1(x))
         x = self.layer4(self.layer3(self.layer2(self.layer1(x))))
         x = self.avgpool(x).flatten(1)
         return self.fc(x)

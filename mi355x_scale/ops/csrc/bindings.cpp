@@ -61,9 +61,10 @@ extern "C" void launch_groupfit_final(
     int T, long long G, int KX, hipStream_t stream);
 
 extern "C" void launch_stem_conv_fwd(const void* x, const void* w, void* out,
-                                     void* wp_scratch,
+                                     void* wp_scratch, float* partial,
                                      int Nb, int H, int W, int HO, int WO,
                                      hipStream_t stream, int phase_mask);
+extern "C" int stem_fwd_stat_blocks(int Nb, int HO);
 extern "C" void launch_stem_conv_wrw(const void* x, const void* dy,
                                      float* dw_f32, void* dw_bf16,
                                      int Nb, int H, int W, int HO, int WO,
@@ -658,9 +659,16 @@ void adam_step_mixed(torch::Tensor master, torch::Tensor gb,
 
 // Stem conv (7x7 s2 p3, 3->64, NHWC bf16): out = conv(x, w).
 // x [N,H,W,3] bf16 channels-last storage, w [64,3,7,7] channels_last,
-// out [N,HO,WO,64].
+// out [N,HO,WO,64]. With ``partial`` (fp32, 2*64*stem_fwd_blocks(N, HO)
+// elements) the multi-row kernel runs and also leaves the per-block BN
+// channel sums there, in the [2C][nblocks] layout bn_fwd_finalize reads.
+int64_t stem_fwd_blocks(int64_t Nb, int64_t HO) {
+  return stem_fwd_stat_blocks((int)Nb, (int)HO);
+}
+
 void stem_conv_fwd(torch::Tensor x, torch::Tensor w, torch::Tensor out,
-                   torch::Tensor wp_scratch, int64_t phase_mask = 7) {
+                   torch::Tensor wp_scratch, int64_t phase_mask = 7,
+                   c10::optional<torch::Tensor> partial = c10::nullopt) {
   TORCH_CHECK(x.is_cuda() && x.scalar_type() == torch::kBFloat16);
   TORCH_CHECK(w.is_cuda() && w.scalar_type() == torch::kBFloat16);
   TORCH_CHECK(out.is_cuda() && out.scalar_type() == torch::kBFloat16);
@@ -671,8 +679,21 @@ void stem_conv_fwd(torch::Tensor x, torch::Tensor w, torch::Tensor out,
   TORCH_CHECK(w.numel() == 64 * 7 * 7 * 3);
   TORCH_CHECK(wp_scratch.scalar_type() == torch::kBFloat16 &&
               wp_scratch.numel() == 64 * 160);
+  TORCH_CHECK(x.is_contiguous() && out.is_contiguous() &&
+                  out.size(0) == Nb && HO == (H - 1) / 2 + 1 &&
+                  WO == (W - 1) / 2 + 1,
+              "stem conv: dense NHWC x/out with 7x7 s2 p3 geometry");
+  float* partial_p = nullptr;
+  if (partial.has_value()) {
+    const torch::Tensor& p = *partial;
+    TORCH_CHECK(p.is_cuda() && p.scalar_type() == torch::kFloat32 &&
+                    p.is_contiguous() &&
+                    p.numel() == 2 * 64 * stem_fwd_blocks(Nb, HO),
+                "partial must be fp32 [2*64*stem_fwd_blocks(N, HO)]");
+    partial_p = p.data_ptr<float>();
+  }
   launch_stem_conv_fwd(x.data_ptr(), w.data_ptr(), out.data_ptr(),
-                       wp_scratch.data_ptr(),
+                       wp_scratch.data_ptr(), partial_p,
                        Nb, H, W, HO, WO,
                        at::cuda::getCurrentHIPStream().stream(),
                        (int)phase_mask);
@@ -738,7 +759,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("stem_conv_fwd", &stem_conv_fwd,
         "MFMA stem conv fwd (7x7 s2, 3->64, NHWC bf16)",
         pybind11::arg("x"), pybind11::arg("w"), pybind11::arg("out"),
-        pybind11::arg("wp_scratch"), pybind11::arg("phase_mask") = 7);
+        pybind11::arg("wp_scratch"), pybind11::arg("phase_mask") = 7,
+        pybind11::arg("partial") = pybind11::none());
+  m.def("stem_fwd_blocks", &stem_fwd_blocks,
+        "block (= BN partial slot) count of the fused-statistics stem fwd");
   m.def("stem_conv_wrw", &stem_conv_wrw,
         "MFMA stem conv weight-grad (fp32 accum + bf16 cast)",
         pybind11::arg("x"), pybind11::arg("dy"), pybind11::arg("dw_f32"),

@@ -123,6 +123,27 @@ __global__ __launch_bounds__(256) void bn_fwd_reduce_kernel(
 }
 
 // -------------------------------------------------------------- fwd finalize
+// Per-channel tail shared by both finalize kernels: statistics out,
+// running-stat momentum update, step counter.
+static __device__ __forceinline__ void bn_fwd_finalize_channel(
+    int c, float s, float q, float* __restrict__ mean,
+    float* __restrict__ invstd, float* __restrict__ running_mean,
+    float* __restrict__ running_var, float momentum, float eps,
+    long long rows, int update_running,
+    long long* __restrict__ num_batches_tracked) {
+  float n = (float)rows;
+  float m = s / n;
+  float var = fmaxf(q / n - m * m, 0.f);
+  mean[c] = m;
+  invstd[c] = rsqrtf(var + eps);
+  if (update_running) {
+    float unbiased = rows > 1 ? var * (n / (n - 1.f)) : var;
+    running_mean[c] = (1.f - momentum) * running_mean[c] + momentum * m;
+    running_var[c] = (1.f - momentum) * running_var[c] + momentum * unbiased;
+  }
+  if (c == 0 && num_batches_tracked) *num_batches_tracked += 1;
+}
+
 // One 64-lane wavefront per channel: lanes stride the [nblocks] partial
 // run (coalesced), then an in-wavefront shuffle tree. mean/invstd out +
 // momentum update of running stats (unbiased running var, matching torch
@@ -150,17 +171,61 @@ __global__ __launch_bounds__(256) void bn_fwd_finalize_kernel(
     q += __shfl_down(q, off, 64);
   }
   if (lane != 0) return;
-  float n = (float)rows;
-  float m = s / n;
-  float var = fmaxf(q / n - m * m, 0.f);
-  mean[c] = m;
-  invstd[c] = rsqrtf(var + eps);
-  if (update_running) {
-    float unbiased = rows > 1 ? var * (n / (n - 1.f)) : var;
-    running_mean[c] = (1.f - momentum) * running_mean[c] + momentum * m;
-    running_var[c] = (1.f - momentum) * running_var[c] + momentum * unbiased;
+  bn_fwd_finalize_channel(c, s, q, mean, invstd, running_mean, running_var,
+                          momentum, eps, rows, update_running,
+                          num_batches_tracked);
+}
+
+// Same result layout, for LONG partial runs: one 256-thread block per
+// channel instead of one wavefront. The stem conv's epilogue leaves one
+// slot per block of its own grid (2,968 at the flagship shape against the
+// reduce kernels' <= 512): a single wavefront then walks 46 dependent
+// iterations per channel (measured 19.3 us against 9.7 us at 512 slots).
+// Lanes stride the run with four independent loads in flight, then
+// shuffle tree per wavefront and a fixed-order sum of the four wavefront
+// totals: deterministic.
+__global__ __launch_bounds__(256) void bn_fwd_finalize_wide_kernel(
+    const float* __restrict__ partial, int nblocks,
+    float* __restrict__ mean, float* __restrict__ invstd,
+    float* __restrict__ running_mean, float* __restrict__ running_var,
+    float momentum, float eps, long long rows, int C, int update_running,
+    long long* __restrict__ num_batches_tracked) {
+  const int c = blockIdx.x;
+  const int tid = threadIdx.x;
+  const float* ps = partial + (long long)c * nblocks;
+  const float* pq = partial + (long long)(C + c) * nblocks;
+  float s4[4] = {0.f, 0.f, 0.f, 0.f}, q4[4] = {0.f, 0.f, 0.f, 0.f};
+  int b = tid;
+  for (; b + 3 * 256 < nblocks; b += 4 * 256) {
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      s4[u] += ps[b + u * 256];
+      q4[u] += pq[b + u * 256];
+    }
   }
-  if (c == 0 && num_batches_tracked) *num_batches_tracked += 1;
+  for (; b < nblocks; b += 256) {
+    s4[0] += ps[b];
+    q4[0] += pq[b];
+  }
+  float s = (s4[0] + s4[1]) + (s4[2] + s4[3]);
+  float q = (q4[0] + q4[1]) + (q4[2] + q4[3]);
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    s += __shfl_down(s, off, 64);
+    q += __shfl_down(q, off, 64);
+  }
+  __shared__ float ws[4], wq[4];
+  if ((tid & 63) == 0) {
+    ws[tid >> 6] = s;
+    wq[tid >> 6] = q;
+  }
+  __syncthreads();
+  if (tid != 0) return;
+  s = (ws[0] + ws[1]) + (ws[2] + ws[3]);
+  q = (wq[0] + wq[1]) + (wq[2] + wq[3]);
+  bn_fwd_finalize_channel(c, s, q, mean, invstd, running_mean, running_var,
+                          momentum, eps, rows, update_running,
+                          num_batches_tracked);
 }
 
 // ---------------------------------------------------------------- fwd apply
@@ -787,6 +852,11 @@ extern "C" void launch_bn_fwd_reduce(const void* x, float* partial,
                      stream, (const bf16*)x, partial, rows, C);
 }
 
+// Above this many partial slots per channel the block-per-channel
+// finalize runs. Every reduce kernel of this file stays below it
+// (bn_reduce_blocks caps at 512), so their results are untouched.
+#define BN_FINALIZE_WIDE_MIN 1024
+
 extern "C" void launch_bn_fwd_finalize(const float* partial, int nblocks,
                                        float* mean, float* invstd,
                                        float* running_mean,
@@ -795,6 +865,13 @@ extern "C" void launch_bn_fwd_finalize(const float* partial, int nblocks,
                                        int update_running,
                                        long long* num_batches_tracked,
                                        hipStream_t stream) {
+  if (nblocks > BN_FINALIZE_WIDE_MIN) {  // long runs: a block per channel
+    hipLaunchKernelGGL(bn_fwd_finalize_wide_kernel, dim3(C), dim3(256), 0,
+                       stream, partial, nblocks, mean, invstd, running_mean,
+                       running_var, momentum, eps, rows, C, update_running,
+                       num_batches_tracked);
+    return;
+  }
   // 4 wavefronts (= 4 channels) per block
   hipLaunchKernelGGL(bn_fwd_finalize_kernel, dim3((C + 3) / 4),
                      dim3(256), 0, stream, partial, nblocks, mean, invstd,

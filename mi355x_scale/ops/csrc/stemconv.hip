@@ -260,6 +260,230 @@ extern "C" __global__ __launch_bounds__(256) void stem_conv_fwd_kernel(
   }
 }
 
+// ------------------------------------------- forward + BN batch statistics
+// v4: a block owns FWD_ROWS consecutive output rows of ONE image (tail
+// chunk shorter when FWD_ROWS does not divide HO). What changes against
+// the kernel above, with the MFMA sequence itself untouched (same
+// operands, same K order -> bit-identical bf16 output):
+//   * the whole (2*rows+5)-row input band is staged ONCE, pads and
+//     out-of-image rows written as zeros in the same pass (no separate
+//     zeroing pass, no barrier between them, one barrier per block);
+//     neighbouring output rows share five of seven input rows, so the
+//     input is read ~1.3x instead of 3.5x and the row loop is barrier-free;
+//   * the 20 weight B-fragments live in registers across the row loop
+//     (80 VGPRs) instead of being re-read from L1 for every row: 80 KB of
+//     vector-memory traffic per output row against 14 KB of output;
+//   * the D fragments go through a wave-private LDS tile and leave as
+//     16-byte-per-lane stores on consecutive addresses (1 KB per
+//     wavefront instruction; the old epilogue issued 32 two-byte stores
+//     per lane, four 32-byte runs per instruction);
+//   * while the rounded values are in registers, each lane accumulates
+//     sum / sum-of-squares for its four channels (fp32, px >= WO
+//     excluded); after the row loop: lanes -> waves -> ONE slot of the
+//     channel-major [2*CO][nblocks] partial layout bn_fwd_finalize_kernel
+//     reads. No atomics, no cross-block traffic: fixed summation order,
+//     deterministic under graph replay.
+// LDS: band 21 rows (34,272 B) + 4 wave tiles (18,432 B) = 52,704 B ->
+// 3 blocks/CU, which is also what the register budget (168) allows.
+#define FWD_ROWS 8
+#define FWD_BAND_ROWS (2 * FWD_ROWS + KH - STRIDE)   // 21
+#define OTROW 72   // tile row stride (els): 144 B keeps the four px
+                   // groups of a D-fragment store on disjoint banks and
+                   // every 8-channel vector 16-byte aligned
+#define XTCH (XTROW / 4)  // short4 chunks per band row (204)
+// loads a thread keeps in flight while staging: 21 rows x 204 chunks over
+// 256 threads is 17 per thread, so the whole band is one round trip
+#define STAGE_DEPTH 17
+
+// Stage ``nrows_in`` input rows starting at ih0 into the band, every
+// element of every row written exactly once: data where the tap is
+// inside the image, zero for the lead/tail pads and out-of-image rows.
+__device__ __forceinline__ void stage_band_rows(
+    const bf16* __restrict__ x, bf16* xt, int n, int ih0, int nrows_in,
+    int H, int W, int tid, int nthreads) {
+  const int rowlen = W * CI;
+  if ((rowlen & 3) == 0) {
+    const int nch = rowlen >> 2;
+    const int total = nrows_in * XTCH;
+    const bf16x4 z = {(bf16)0.0f, (bf16)0.0f, (bf16)0.0f, (bf16)0.0f};
+    for (int base = 0; base < total; base += nthreads * STAGE_DEPTH) {
+      bf16x4 v[STAGE_DEPTH];
+#pragma unroll
+      for (int u = 0; u < STAGE_DEPTH; ++u) {
+        const int i = base + tid + u * nthreads;
+        v[u] = z;
+        if (i < total) {
+          const int r = i / XTCH, c = i - r * XTCH - XTOFF / 4;
+          const int ih = ih0 + r;
+          if (ih >= 0 && ih < H && c >= 0 && c < nch)
+            v[u] = reinterpret_cast<const bf16x4*>(
+                x + ((long long)n * H + ih) * rowlen)[c];
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < STAGE_DEPTH; ++u) {
+        const int i = base + tid + u * nthreads;
+        if (i < total) reinterpret_cast<bf16x4*>(xt)[i] = v[u];
+      }
+    }
+  } else {  // odd row length (test shapes): scalar fallback
+    const int total = nrows_in * XTROW;
+    for (int i = tid; i < total; i += nthreads) {
+      const int r = i / XTROW, e = i - r * XTROW - XTOFF;
+      const int ih = ih0 + r;
+      bf16 v = (bf16)0.0f;
+      if (ih >= 0 && ih < H && e >= 0 && e < rowlen)
+        v = x[((long long)n * H + ih) * rowlen + e];
+      xt[i] = v;
+    }
+  }
+}
+
+// grid = Nb * ceil(HO / FWD_ROWS); partial is fp32 [2*CO][gridDim.x]
+extern "C" __global__ __launch_bounds__(256, 3) void stem_conv_fwd_stats_kernel(
+    const bf16* __restrict__ x,   // [N][H][W][CI]
+    const bf16* __restrict__ wp,  // [CO][KPAD] padded (stem_pad_weights)
+    bf16* __restrict__ out,       // [N][HO][WO][CO]
+    float* __restrict__ partial,  // [2*CO][nblocks]
+    int Nb, int H, int W, int HO, int WO, int nchunks, int phase_mask) {
+  __shared__ __attribute__((aligned(16))) bf16 xt[FWD_BAND_ROWS * XTROW];
+  __shared__ __attribute__((aligned(16))) bf16 ot[4 * 32 * OTROW];
+  // byte offsets (relative to band row 2*rr, pixel 0) of the 40 taps a
+  // lane gathers, one 40-entry run per k-group. Per-lane address math
+  // hoisted out of the row loop costs 80 registers and spills the
+  // weights; the table costs five broadcast 16-byte LDS reads per M-tile.
+  __shared__ __attribute__((aligned(16))) unsigned short ktab[4 * KPAD / 4];
+  const int tid = threadIdx.x;
+  const int wave = tid >> 6;
+  const int lane = tid & 63;
+  const int row16 = lane & 15;
+  const int kgrp = lane >> 4;
+  const int n = blockIdx.x / nchunks;
+  const int ho0 = (blockIdx.x - n * nchunks) * FWD_ROWS;
+  const int rows = min(FWD_ROWS, HO - ho0);
+
+  // weight fragments: issued first so their latency hides under staging
+  bf16x8 bfrag[KPAD / 32][4];
+#pragma unroll
+  for (int kk = 0; kk < KPAD / 32; ++kk)
+#pragma unroll
+    for (int c = 0; c < 4; ++c)
+      bfrag[kk][c] = *reinterpret_cast<const bf16x8*>(
+          wp + (c * 16 + row16) * KPAD + kk * 32 + kgrp * 8);
+
+  if (tid < 4 * KPAD / 4) {
+    const int g = tid / (KPAD / 4), i = tid - g * (KPAD / 4);
+    const int k = (i >> 3) * 32 + g * 8 + (i & 7);
+    ktab[tid] = (unsigned short)(2 * koff_of(min(k, KTAP - 1)));
+  }
+  if (phase_mask & 1)
+    stage_band_rows(x, xt, n, ho0 * STRIDE - PADDING,
+                    rows * STRIDE + KH - STRIDE, H, W, tid, 256);
+  __syncthreads();
+  if (!(phase_mask & 4)) return;
+
+  float ssum[4] = {0.f, 0.f, 0.f, 0.f}, ssq[4] = {0.f, 0.f, 0.f, 0.f};
+  const int pxb0 = (wave * 32 + row16) * (STRIDE * CI);
+  const int pxb1 = (wave * 32 + 16 + row16) * (STRIDE * CI);
+  bf16* tw = ot + wave * 32 * OTROW;   // this wave's 32 px x 64 co tile
+#pragma unroll 1
+  for (int rr = 0; rr < rows; ++rr) {
+    const int rshift = rr * STRIDE * XTROW;
+    // one 16-px M-tile at a time (a real loop: 16 accumulators live, not
+    // 32, so the weights stay in registers); each accumulator still sees
+    // its five K-steps in the same order
+#pragma unroll 1
+    for (int m = 0; m < 2; ++m) {
+      f32x4 acc[4];
+#pragma unroll
+      for (int c = 0; c < 4; ++c) acc[c] = (f32x4)0.0f;
+      const unsigned rb = 2u * (unsigned)(rshift + (m ? pxb1 : pxb0));
+      const uint4* tp = reinterpret_cast<const uint4*>(ktab) + kgrp * 5;
+      asm volatile("" : "+v"(tp));  // re-read per tile, do not hoist
+#pragma unroll
+      for (int kk = 0; kk < KPAD / 32; ++kk) {
+        const uint4 t4 = tp[kk];
+        const unsigned tk[4] = {t4.x, t4.y, t4.z, t4.w};
+        bf16x8 f;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          const int k = kk * 32 + kgrp * 8 + j;
+          // K-padding taps read xt[0], row 0's lead pad: always zero
+          const bool kz = (kk == KPAD / 32 - 1) && k >= KTAP;
+          const unsigned pk = tk[j >> 1];
+          const unsigned ob = ((j & 1) ? (pk >> 16) : (pk & 0xffffu)) + rb;
+          f[j] = *reinterpret_cast<const bf16*>(
+              reinterpret_cast<const char*>(xt) + (kz ? 0u : ob));
+        }
+#pragma unroll
+        for (int c = 0; c < 4; ++c)
+          acc[c] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+              f, bfrag[kk][c], acc[c], 0, 0, 0);
+      }
+      // D col = lane&15 (co), row = 4*(lane>>4)+r (px): round, count
+      // into the statistics, and transpose through the wave's tile
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int pxl = m * 16 + kgrp * 4 + r;
+        const bool live = wave * 32 + pxl < WO;
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+          const bf16 v = (bf16)acc[c][r];
+          tw[pxl * OTROW + c * 16 + row16] = v;
+          const float f = live ? (float)v : 0.f;
+          ssum[c] += f;
+          ssq[c] += f * f;
+        }
+      }
+    }
+    // the tile is wave-private and a wave's LDS operations complete in
+    // order, so wave-scope ordering is all the hand-over needs
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    const long long rowbase = ((long long)n * HO + ho0 + rr) * WO;
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      const int v = lane + t * 64;
+      const int pxl = v >> 3, j8 = (v & 7) * 8;
+      const int px = wave * 32 + pxl;
+      const bf16x8 val = *reinterpret_cast<const bf16x8*>(
+          tw + pxl * OTROW + j8);
+      if (px < WO)
+        *reinterpret_cast<bf16x8*>(out + (rowbase + px) * CO + j8) = val;
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  }
+
+  // statistics: the four px groups of a wave, then the four waves (fixed
+  // order), then this block's slot
+#pragma unroll
+  for (int c = 0; c < 4; ++c) {
+    ssum[c] += __shfl_xor(ssum[c], 16, 64);
+    ssum[c] += __shfl_xor(ssum[c], 32, 64);
+    ssq[c] += __shfl_xor(ssq[c], 16, 64);
+    ssq[c] += __shfl_xor(ssq[c], 32, 64);
+  }
+  float* red = reinterpret_cast<float*>(tw);  // own tile: reads are done
+  if (kgrp == 0) {
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      red[c * 16 + row16] = ssum[c];
+      red[CO + c * 16 + row16] = ssq[c];
+    }
+  }
+  __syncthreads();
+  if (tid < 2 * CO) {
+    float t = 0.f;
+#pragma unroll
+    for (int w = 0; w < 4; ++w)
+      t += reinterpret_cast<const float*>(ot + w * 32 * OTROW)[tid];
+    partial[(long long)tid * gridDim.x + blockIdx.x] = t;
+  }
+}
+
 // ---------------------------------------------------------------- wrw
 // block = 256 threads (4 waves) loops over ``rows_per_block`` output
 // rows; per row: band stage + dy-row stage, then each wave reduces ALL
@@ -421,13 +645,29 @@ extern "C" __global__ __launch_bounds__(256) void stem_wrw_cast_kernel(
   }
 }
 
+// Blocks (= statistics slots per channel) of the fused-statistics forward.
+extern "C" int stem_fwd_stat_blocks(int Nb, int HO) {
+  return Nb * ((HO + FWD_ROWS - 1) / FWD_ROWS);
+}
+
+// ``partial`` null: the one-row-per-block kernel, no statistics (the BN
+// reduce then reads the map back). Non-null: fp32 [2*CO][
+// stem_fwd_stat_blocks] scratch, filled with the per-block channel sums.
 extern "C" void launch_stem_conv_fwd(const void* x, const void* w, void* out,
-                                     void* wp_scratch,
+                                     void* wp_scratch, float* partial,
                                      int Nb, int H, int W, int HO, int WO,
                                      hipStream_t stream, int phase_mask) {
   hipLaunchKernelGGL(stem_pad_weights_kernel,
                      dim3((CO * KPAD + 255) / 256), dim3(256), 0, stream,
                      (const bf16*)w, (bf16*)wp_scratch);
+  if (partial) {
+    const int nchunks = (HO + FWD_ROWS - 1) / FWD_ROWS;
+    hipLaunchKernelGGL(stem_conv_fwd_stats_kernel, dim3(Nb * nchunks),
+                       dim3(256), 0, stream, (const bf16*)x,
+                       (const bf16*)wp_scratch, (bf16*)out, partial,
+                       Nb, H, W, HO, WO, nchunks, phase_mask);
+    return;
+  }
   hipLaunchKernelGGL(stem_conv_fwd_kernel, dim3(Nb * HO), dim3(256), 0,
                      stream, (const bf16*)x, (const bf16*)wp_scratch,
                      (bf16*)out, Nb, H, W, HO, WO, phase_mask);

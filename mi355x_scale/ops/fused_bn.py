@@ -27,6 +27,11 @@ registers from the pooled grad and the u8 window codes
 and on the HIP training path ``bn_fwd_finalize`` bumps
 ``num_batches_tracked`` on the device, so no per-BN ``+= 1`` kernel runs.
 
+Round 4: ``forward_pooled`` accepts the per-block channel sums the stem
+conv's epilogue already produced (``StemConv2d.forward_with_stats``) and
+then skips ``bn_fwd_reduce``: the 340 MB stem map is not read back for its
+statistics.
+
 All device work is stream-ordered with no host sync, so the op captures
 into hipGraphs (train/graphstep.py).
 """
@@ -150,14 +155,17 @@ class _FusedBNPoolFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, weight, bias, running_mean, running_var,
-                momentum, eps, training, num_batches_tracked):
+                momentum, eps, training, num_batches_tracked, partial=None):
         C = x.shape[1]
         dev = x.device
         if training:
             rows = x.numel() // C
             mean = torch.empty(C, dtype=torch.float32, device=dev)
             invstd = torch.empty(C, dtype=torch.float32, device=dev)
-            partial = _C.bn_fwd_reduce(x, C)
+            # a ready-made partial (the stem conv's epilogue sums, same
+            # [2C][nblocks] layout) replaces the full read of x
+            if partial is None:
+                partial = _C.bn_fwd_reduce(x, C)
             # the finalize kernel also bumps the step counter
             _C.bn_fwd_finalize(partial, mean, invstd, running_mean,
                                running_var, momentum, eps, rows, C, True,
@@ -228,7 +236,7 @@ class _FusedBNPoolFn(torch.autograd.Function):
             _C.bn_bwd_apply_rm(dz, x, mean, invstd, bias, k, dx, C)
         return (dx, None if fuse_acc else dweight,
                 None if fuse_acc else dbias, None, None, None, None, None,
-                None)
+                None, None)
 
 
 class FusedBNReLU2d(nn.Module):
@@ -261,10 +269,15 @@ class FusedBNReLU2d(nn.Module):
         return (f"{self.num_features}, eps={self.eps}, "
                 f"momentum={self.momentum}, relu={self.relu}")
 
-    def forward_pooled(self, x: torch.Tensor) -> torch.Tensor:
+    def forward_pooled(self, x: torch.Tensor,
+                       partial: Optional[torch.Tensor] = None
+                       ) -> torch.Tensor:
         """``maxpool3x3s2(relu(bn(x)))`` with the normalized map never
         materialized (stem fusion; relu layers without residual only).
-        Falls back to the composed ops off the GPU bf16 path."""
+        ``partial``: per-block channel sums of ``x`` already produced by
+        the kernel that wrote it (``StemConv2d.forward_with_stats``); in
+        training mode on the HIP path the reduce pass over ``x`` is then
+        skipped. Falls back to the composed ops off the GPU bf16 path."""
         assert self.relu, "pooled fusion is relu-only"
         if _hip_supported(x):
             require_ext()
@@ -274,7 +287,8 @@ class FusedBNReLU2d(nn.Module):
             return _FusedBNPoolFn.apply(
                 x, self.weight, self.bias, self.running_mean,
                 self.running_var, self.momentum, self.eps, self.training,
-                self.num_batches_tracked)
+                self.num_batches_tracked,
+                partial if self.training else None)
         return F.max_pool2d(self.forward(x), 3, stride=2, padding=1)
 
     def forward(self, x: torch.Tensor,

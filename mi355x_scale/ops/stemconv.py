@@ -10,6 +10,15 @@ weights read from L1-resident global), weight-grad 267 us (1.12x;
 ring-band staging + a software-pipelined dy stage prefetched into
 registers under the MFMA phase).
 
+The default forward kernel (``MI355X_STEM_FUSED_STATS``, ``0`` = the
+one-row-per-block kernel above) gives a block eight output rows: the
+input band is staged once, the weights stay in registers across the
+rows, the output leaves as 16-byte stores, and the epilogue sums the
+BN batch statistics of the values it stores into one partial slot per
+block (``forward_with_stats`` hands them to
+``FusedBNReLU2d.forward_pooled``, which then skips its reduce pass).
+The bf16 output is bit-identical to the one-row kernel's.
+
 ``StemConv2d`` subclasses ``nn.Conv2d`` (state-dict compatible, same
 init); the HIP path engages on CUDA bf16 channels-last inputs with the
 exact stem geometry, everything else falls back to ``F.conv2d`` (the
@@ -27,36 +36,79 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 
+def fused_stats_enabled() -> bool:
+    """``MI355X_STEM_FUSED_STATS=0`` selects the one-row-per-block forward
+    kernel and the separate BN reduce over its output (A/B runs, tests)."""
+    return os.environ.get("MI355X_STEM_FUSED_STATS", "1") != "0"
+
+
+def _stem_forward(x: torch.Tensor, weight: torch.Tensor, fused: bool):
+    """Launch the forward conv. ``fused``: the multi-row kernel, which also
+    fills the BN partial sums of its output (fp32 ``[2*64][nblocks]``, the
+    layout ``bn_fwd_finalize`` reads); otherwise ``partial`` is None."""
+    from . import _C
+    N, C, H, W = x.shape
+    HO = (H + 2 * 3 - 7) // 2 + 1
+    WO = (W + 2 * 3 - 7) // 2 + 1
+    out = torch.empty((N, 64, HO, WO), dtype=torch.bfloat16,
+                      device=x.device,
+                      memory_format=torch.channels_last)
+    # kernels address raw NHWC storage: hand the physical views over
+    wp = torch.empty(64 * 160, dtype=torch.bfloat16, device=x.device)
+    partial = None
+    if fused:
+        partial = torch.empty(2 * 64 * _C.stem_fwd_blocks(N, HO),
+                              dtype=torch.float32, device=x.device)
+    _C.stem_conv_fwd(x.permute(0, 2, 3, 1), weight.permute(0, 2, 3, 1),
+                     out.permute(0, 2, 3, 1), wp, 7, partial)
+    return out, partial
+
+
+def _stem_backward(ctx, dy: torch.Tensor):
+    from . import _C
+    x, weight = ctx.saved_tensors
+    if dy.dtype != torch.bfloat16:
+        dy = dy.to(torch.bfloat16)
+    dy = dy.contiguous(memory_format=torch.channels_last)
+    dw = torch.empty_like(weight)
+    scratch = torch.empty(64 * 160, dtype=torch.float32,
+                          device=x.device)
+    _C.stem_conv_wrw(x.permute(0, 2, 3, 1), dy.permute(0, 2, 3, 1),
+                     scratch, dw.permute(0, 2, 3, 1))
+    return None, dw
+
+
 class _StemConvFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x: torch.Tensor, weight: torch.Tensor):
-        from . import _C
-        N, C, H, W = x.shape
-        HO = (H + 2 * 3 - 7) // 2 + 1
-        WO = (W + 2 * 3 - 7) // 2 + 1
-        out = torch.empty((N, 64, HO, WO), dtype=torch.bfloat16,
-                          device=x.device,
-                          memory_format=torch.channels_last)
-        # kernels address raw NHWC storage: hand the physical views over
-        wp = torch.empty(64 * 160, dtype=torch.bfloat16, device=x.device)
-        _C.stem_conv_fwd(x.permute(0, 2, 3, 1), weight.permute(0, 2, 3, 1),
-                         out.permute(0, 2, 3, 1), wp)
+        out, _ = _stem_forward(x, weight, fused_stats_enabled())
         ctx.save_for_backward(x, weight)
         return out
 
     @staticmethod
     def backward(ctx, dy: torch.Tensor):
-        from . import _C
-        x, weight = ctx.saved_tensors
-        if dy.dtype != torch.bfloat16:
-            dy = dy.to(torch.bfloat16)
-        dy = dy.contiguous(memory_format=torch.channels_last)
-        dw = torch.empty_like(weight)
-        scratch = torch.empty(64 * 160, dtype=torch.float32,
-                              device=x.device)
-        _C.stem_conv_wrw(x.permute(0, 2, 3, 1), dy.permute(0, 2, 3, 1),
-                         scratch, dw.permute(0, 2, 3, 1))
-        return None, dw
+        return _stem_backward(ctx, dy)
+
+
+class _StemConvStatsFn(torch.autograd.Function):
+    """Forward conv that also returns the BN partial sums of its output
+    (non-differentiable); backward is ``_StemConvFn``'s."""
+
+    @staticmethod
+    def forward(ctx, x: torch.Tensor, weight: torch.Tensor):
+        out, partial = _stem_forward(x, weight, True)
+        ctx.save_for_backward(x, weight)
+        ctx.mark_non_differentiable(partial)
+        # otherwise autograd hands backward a zero-filled tensor of
+        # partial's size every step (a 1.5 MB fill kernel at bs 212)
+        ctx.set_materialize_grads(False)
+        return out, partial
+
+    @staticmethod
+    def backward(ctx, dy, _dpartial):
+        if dy is None:
+            return None, None
+        return _stem_backward(ctx, dy)
 
 
 class StemConv2d(nn.Conv2d):
@@ -76,6 +128,18 @@ class StemConv2d(nn.Conv2d):
                 and self.weight.is_contiguous(
                     memory_format=torch.channels_last)
                 and not x.requires_grad)  # stem input never needs dx
+
+    def stats_ok(self, x: torch.Tensor) -> bool:
+        """True when ``forward_with_stats`` will run the fused kernel."""
+        return fused_stats_enabled() and self._hip_ok(x)
+
+    def forward_with_stats(self, x: torch.Tensor):
+        """``(conv(x), partial)``: ``partial`` holds the per-block BN sums
+        of the output for ``FusedBNReLU2d.forward_pooled``, or is None
+        when the HIP path does not engage or the switch is off."""
+        if self.stats_ok(x):
+            return _StemConvStatsFn.apply(x, self.weight)
+        return self.forward(x), None
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         if self._hip_ok(x):
