@@ -34,6 +34,19 @@ def _conv1x1(cin: int, cout: int, stride: int = 1) -> nn.Conv2d:
     return nn.Conv2d(cin, cout, 1, stride=stride, bias=False)
 
 
+def _join_twin(x: torch.Tensor) -> torch.Tensor:
+    """The tensor a block's skip path should read. The previous block's
+    closing ``FusedBNReLU2d`` hands over its output as two autograd outputs
+    over one storage (ops/fused_bn.py): ``x`` itself and a twin riding on
+    it. conv1 reads ``x`` and the identity / downsample reads the twin, so
+    the two gradients reach that BN's backward unsummed and its reduce
+    kernel adds them. Any other tensor (stem output, CPU path, eval, a
+    tensor swapped in by a forward hook) has no twin: both paths read ``x``
+    and autograd adds."""
+    twin = getattr(x, FusedBNReLU2d.JOIN_ATTR, None)
+    return x if twin is None else twin
+
+
 class BasicBlock(nn.Module):
     expansion = 1
 
@@ -47,7 +60,8 @@ class BasicBlock(nn.Module):
         self.downsample = downsample
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
-        identity = x if self.downsample is None else self.downsample(x)
+        skip = _join_twin(x)
+        identity = skip if self.downsample is None else self.downsample(skip)
         out = self.bn1(self.conv1(x))
         return self.bn2(self.conv2(out), residual=identity)
 
@@ -67,7 +81,8 @@ class Bottleneck(nn.Module):
         self.downsample = downsample
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
-        identity = x if self.downsample is None else self.downsample(x)
+        skip = _join_twin(x)
+        identity = skip if self.downsample is None else self.downsample(skip)
         out = self.bn1(self.conv1(x))
         out = self.bn2(self.conv2(out))
         return self.bn3(self.conv3(out), residual=identity)

@@ -201,6 +201,13 @@ extern "C" void launch_bn_bwd_reduce(const void* dz, const void* y,
                                      const float* invstd, float* partial,
                                      void* dym, int nblocks, long long rows,
                                      int C, int relu, hipStream_t stream);
+extern "C" void launch_bn_bwd_reduce_join(const void* dz1, const void* dz2,
+                                          const void* y, const void* x,
+                                          const float* mean,
+                                          const float* invstd,
+                                          float* partial, void* dym,
+                                          int nblocks, long long rows, int C,
+                                          int relu, hipStream_t stream);
 extern "C" void launch_bn_bwd_reduce_rm(const void* dz, const void* x,
                                         const float* mean,
                                         const float* invstd,
@@ -331,6 +338,43 @@ torch::Tensor bn_bwd_reduce(torch::Tensor dz, torch::Tensor y,
                        partial.data_ptr<float>(), dym_p, nb, rows, (int)C,
                        relu ? 1 : 0,
                        at::cuda::getCurrentHIPStream().stream());
+  return partial;
+}
+
+// Joined residual-layer reduce: the layer's output had two consumers and
+// (dz1, dz2) are their gradients, summed (bf16-rounded, as autograd's add
+// would have stored them) inside the kernel. dym is mandatory here.
+torch::Tensor bn_bwd_reduce_join(torch::Tensor dz1, torch::Tensor dz2,
+                                 torch::Tensor y, torch::Tensor x,
+                                 torch::Tensor mean, torch::Tensor invstd,
+                                 torch::Tensor dym, int64_t C, bool relu) {
+  _check_bn_act(dz1, "dz1"); _check_bn_act(dz2, "dz2");
+  _check_bn_act(y, "y"); _check_bn_act(x, "x"); _check_bn_act(dym, "dym");
+  _check_f32(mean, "mean"); _check_f32(invstd, "invstd");
+  TORCH_CHECK(mean.numel() == C && invstd.numel() == C,
+              "mean/invstd must have C elements");
+  // every map is indexed with x's NHWC offsets: same shape, same dense
+  // channels-last strides
+  TORCH_CHECK(x.dim() == 4 && x.size(1) == C &&
+                  x.is_contiguous(at::MemoryFormat::ChannelsLast),
+              "x must be a channels_last [N,C,H,W] tensor");
+  const torch::Tensor* maps[] = {&dz1, &dz2, &y, &dym};
+  const char* names[] = {"dz1", "dz2", "y", "dym"};
+  for (int i = 0; i < 4; ++i)
+    TORCH_CHECK(maps[i]->sizes() == x.sizes() &&
+                    maps[i]->is_contiguous(at::MemoryFormat::ChannelsLast),
+                names[i], " must match x (channels_last)");
+  long long rows = _bn_rows(x, C);
+  int nb = bn_reduce_blocks(rows, (int)C);
+  auto partial = torch::empty(
+      {(int64_t)nb * 2 * C},
+      torch::TensorOptions().dtype(torch::kFloat32).device(x.device()));
+  launch_bn_bwd_reduce_join(dz1.data_ptr(), dz2.data_ptr(), y.data_ptr(),
+                            x.data_ptr(), mean.data_ptr<float>(),
+                            invstd.data_ptr<float>(),
+                            partial.data_ptr<float>(), dym.data_ptr(), nb,
+                            rows, (int)C, relu ? 1 : 0,
+                            at::cuda::getCurrentHIPStream().stream());
   return partial;
 }
 
@@ -788,6 +832,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         pybind11::arg("num_batches_tracked") = pybind11::none());
   m.def("bn_fwd_apply", &bn_fwd_apply);
   m.def("bn_bwd_reduce", &bn_bwd_reduce);
+  m.def("bn_bwd_reduce_join", &bn_bwd_reduce_join);
   m.def("bn_bwd_reduce_rm", &bn_bwd_reduce_rm);
   m.def("bn_bwd_apply_rm", &bn_bwd_apply_rm);
   m.def("bn_bwd_finalize", &bn_bwd_finalize);

@@ -36,7 +36,10 @@
 //   * stem backward (bn_pool_bwd_*): the max-unpool of the pooled
 //     gradient is rebuilt in registers inside both passes, so the
 //     un-pooled map is never written or read;
-//   * bn_fwd_finalize also bumps the module's num_batches_tracked.
+//   * bn_fwd_finalize also bumps the module's num_batches_tracked;
+//   * joined residual backward (bn_bwd_reduce_join): a block output has
+//     two consumers, and the reduce reads their two gradients itself, so
+//     autograd's stand-alone add of the two maps does not run.
 //
 // Reference parity: this implements the BatchNorm2d semantics the
 // reference's torchvision resnet50 relies on
@@ -315,6 +318,91 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(
       if (WRITE_DY) dyv.h[j] = __float2bfloat16(dy);
     }
     if (WRITE_DY) store8(dym + off, dyv);
+  }
+
+  __shared__ float lds[256 * 2 * VEC];
+  float* mys = &lds[(rsub * lanes + lane) * 2 * VEC];
+#pragma unroll
+  for (int j = 0; j < VEC; ++j) {
+    mys[j] = sdy[j];
+    mys[VEC + j] = sdyx[j];
+  }
+  __syncthreads();
+  for (int step = rows_per_iter >> 1; step > 0; step >>= 1) {
+    if (rsub < step) {
+      const float* other = &lds[((rsub + step) * lanes + lane) * 2 * VEC];
+#pragma unroll
+      for (int j = 0; j < 2 * VEC; ++j) mys[j] += other[j];
+    }
+    __syncthreads();
+  }
+  if (rsub == 0) {
+    // channel-major partial layout [2C][nblocks] (see forward reduce)
+#pragma unroll
+    for (int j = 0; j < VEC; ++j) {
+      partial[(long long)(lane * VEC + j) * gridDim.x + blockIdx.x] = mys[j];
+      partial[(long long)(C + lane * VEC + j) * gridDim.x + blockIdx.x] =
+          mys[VEC + j];
+    }
+  }
+}
+
+// ------------------------------------------------- bwd reduce, joined grads
+// Residual-layer reduce for an output with TWO consumers (the next block's
+// conv1 and its identity path / downsample conv). Autograd would sum the
+// two incoming gradients with a stand-alone elementwise add (2 maps read,
+// 1 written) right in front of this kernel, which reads that sum exactly
+// once. Here the kernel reads both addends itself: one extra map read, no
+// add kernel. Per element dy = bf16(float(dz1) + float(dz2)), widened
+// again — exactly the value the bf16 add kernel stored — so mask, sdy,
+// sdyx and dym are bit-identical to bn_bwd_reduce_kernel<RELU, true> run
+// on the summed map. A sibling kernel rather than a third template flag,
+// so the one-gradient instantiations stay what they are. Grid sizing,
+// LDS tree, partial layout and finalize are the one-gradient kernel's.
+// All four 16 B loads of a row are issued before the first use.
+template <bool RELU>
+__global__ __launch_bounds__(256) void bn_bwd_reduce_join_kernel(
+    const bf16* __restrict__ dz1, const bf16* __restrict__ dz2,
+    const bf16* __restrict__ y, const bf16* __restrict__ x,
+    const float* __restrict__ mean, const float* __restrict__ invstd,
+    float* __restrict__ partial, bf16* __restrict__ dym, long long rows,
+    int C) {
+  const int lanes = C / VEC;
+  const int lane = threadIdx.x % lanes;
+  const int rsub = threadIdx.x / lanes;
+  const int rows_per_iter = blockDim.x / lanes;
+  const long long rstride = (long long)gridDim.x * rows_per_iter;
+
+  float m[VEC], is[VEC];
+#pragma unroll
+  for (int j = 0; j < VEC; ++j) {
+    int c = lane * VEC + j;
+    m[j] = mean[c];
+    is[j] = invstd[c];
+  }
+
+  float sdy[VEC] = {0.f}, sdyx[VEC] = {0.f};
+  for (long long row = (long long)blockIdx.x * rows_per_iter + rsub;
+       row < rows; row += rstride) {
+    const long long off = row * C + (long long)lane * VEC;
+    BVec g1 = load8(dz1 + off);
+    BVec g2 = load8(dz2 + off);
+    BVec xv = load8(x + off);
+    BVec yv;
+    if (RELU) yv = load8(y + off);
+    BVec dyv;
+#pragma unroll
+    for (int j = 0; j < VEC; ++j) {
+      // round the sum to bf16 first: that is what the add kernel stored
+      float dy = __bfloat162float(__float2bfloat16(
+          __bfloat162float(g1.h[j]) + __bfloat162float(g2.h[j])));
+      if (RELU && __bfloat162float(yv.h[j]) <= 0.f) dy = 0.f;
+      float xhat = (__bfloat162float(xv.h[j]) - m[j]) * is[j];
+      sdy[j] += dy;
+      sdyx[j] += dy * xhat;
+      dyv.h[j] = __float2bfloat16(dy);
+    }
+    store8(dym + off, dyv);
   }
 
   __shared__ float lds[256 * 2 * VEC];
@@ -910,6 +998,25 @@ extern "C" void launch_bn_bwd_reduce(const void* dz, const void* y,
   else if (relu) REDUCE(true, false);
   else if (dym) REDUCE(false, true);
   else REDUCE(false, false);
+#undef REDUCE
+}
+
+// Joined form: dz1 + dz2 summed in the kernel; dym is always written.
+extern "C" void launch_bn_bwd_reduce_join(const void* dz1, const void* dz2,
+                                          const void* y, const void* x,
+                                          const float* mean,
+                                          const float* invstd,
+                                          float* partial, void* dym,
+                                          int nblocks, long long rows, int C,
+                                          int relu, hipStream_t stream) {
+  dim3 grid(nblocks), block(256);
+#define REDUCE(R)                                                         \
+  hipLaunchKernelGGL((bn_bwd_reduce_join_kernel<R>), grid, block, 0,      \
+                     stream, (const bf16*)dz1, (const bf16*)dz2,          \
+                     (const bf16*)y, (const bf16*)x, mean, invstd,        \
+                     partial, (bf16*)dym, rows, C)
+  if (relu) REDUCE(true);
+  else REDUCE(false);
 #undef REDUCE
 }
 

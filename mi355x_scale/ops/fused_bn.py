@@ -32,11 +32,22 @@ conv's epilogue already produced (``StemConv2d.forward_with_stats``) and
 then skips ``bn_fwd_reduce``: the 340 MB stem map is not read back for its
 statistics.
 
+Round 5: a residual layer's output is a block output and has two
+consumers (the next block's conv1, and its identity path or downsample
+conv). On the HIP training path ``_FusedBNFn`` returns that output twice
+over one storage; ``BasicBlock`` / ``Bottleneck`` feed one path from each,
+so backward receives the two gradients unsummed and ``bn_bwd_reduce_join``
+adds them while it streams (bf16-rounded, bit-identical to autograd's
+add), and the stand-alone add of two activation-size maps per block no
+longer runs. ``MI355X_BN_JOIN=0`` selects the single-output path for A/B
+runs and tests; ``FusedBNReLU2d.join_calls`` counts joined backwards.
+
 All device work is stream-ordered with no host sync, so the op captures
 into hipGraphs (train/graphstep.py).
 """
 from __future__ import annotations
 
+import os
 from typing import Optional
 
 import torch
@@ -58,7 +69,7 @@ def _hip_supported(x: torch.Tensor) -> bool:
 class _FusedBNFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, residual, weight, bias, running_mean, running_var,
-                momentum, eps, relu, num_batches_tracked):
+                momentum, eps, relu, num_batches_tracked, join=False):
         C = x.shape[1]
         rows = x.numel() // C
         dev = x.device
@@ -78,16 +89,30 @@ class _FusedBNFn(torch.autograd.Function):
                               mean, invstd, weight, bias)
         ctx.relu = relu
         ctx.has_res = residual is not None
-        return y
+        if not join:
+            return y
+        # Two outputs over one storage: a consumer of y and a consumer of
+        # the alias each send their own gradient to backward, UNSUMMED, so
+        # the reduce kernel can add them itself. An unused output's grad
+        # arrives as None instead of a zero-filled map.
+        ctx.set_materialize_grads(False)
+        return y, y.view_as(y)
 
     @staticmethod
-    def backward(ctx, dz):
+    def backward(ctx, dz, dz2=None):
         x, y, mean, invstd, weight, bias = ctx.saved_tensors
         C = x.shape[1]
         rows = x.numel() // C
         dev = x.device
+        if dz is None:
+            dz, dz2 = dz2, None
+        if dz is None:  # joined forward, neither output used
+            return (None,) * 11
         if not dz.is_contiguous(memory_format=torch.channels_last):
             dz = dz.contiguous(memory_format=torch.channels_last)
+        if (dz2 is not None and
+                not dz2.is_contiguous(memory_format=torch.channels_last)):
+            dz2 = dz2.contiguous(memory_format=torch.channels_last)
         k = torch.empty(3 * C, dtype=torch.float32, device=dev)
         # Inside hipGraph capture (the flagship graphed step), write the
         # channel grads straight into the existing flat grad views and
@@ -120,14 +145,23 @@ class _FusedBNFn(torch.autograd.Function):
             # apply pass then reads (dym, x) — one read+write less than
             # re-deriving dy from (dz, y).
             dym = torch.empty_like(x)
-            partial = _C.bn_bwd_reduce(dz, y, x, mean, invstd, dym, C,
-                                       ctx.relu)
+            if dz2 is not None:
+                # both consumers sent a gradient: the reduce sums them
+                # (bf16-rounded like autograd's add) while it streams
+                partial = _C.bn_bwd_reduce_join(dz, dz2, y, x, mean, invstd,
+                                                dym, C, ctx.relu)
+                FusedBNReLU2d.join_calls += 1
+            else:
+                partial = _C.bn_bwd_reduce(dz, y, x, mean, invstd, dym, C,
+                                           ctx.relu)
             _C.bn_bwd_finalize(partial, invstd, weight, dweight, dbias, k,
                                rows, C, fuse_acc)
             _C.bn_bwd_apply_dym(dym, x, mean, invstd, k, dx, C)
             return (dx, dym, None if fuse_acc else dweight,
                     None if fuse_acc else dbias, None, None, None, None,
-                    None, None)
+                    None, None, None)
+        # only residual layers are joined in forward
+        assert dz2 is None
         if ctx.relu:
             # recompute-mask path: one full activation-map read (the
             # stored y) drops out of BOTH backward passes
@@ -145,7 +179,7 @@ class _FusedBNFn(torch.autograd.Function):
                             C, False)
         return (dx, None, None if fuse_acc else dweight,
                 None if fuse_acc else dbias, None, None, None, None, None,
-                None)
+                None, None)
 
 
 class _FusedBNPoolFn(torch.autograd.Function):
@@ -251,6 +285,13 @@ class FusedBNReLU2d(nn.Module):
     # test asserts it (no silent MIOpen fallback).
     gpu_fallbacks: list = []
 
+    # Backward calls that took the joined reduce (two gradients summed in
+    # the kernel, see forward); tests assert the path was taken.
+    join_calls: int = 0
+
+    # Name of the attribute by which a joined output carries its twin.
+    JOIN_ATTR = "_bn_join_twin"
+
     def __init__(self, num_features: int, eps: float = 1e-5,
                  momentum: float = 0.1, relu: bool = True):
         super().__init__()
@@ -301,10 +342,28 @@ class FusedBNReLU2d(nn.Module):
                     memory_format=torch.channels_last)
             if self.training:
                 # bn_fwd_finalize bumps num_batches_tracked on the device
-                return _FusedBNFn.apply(
+                join = (residual is not None and
+                        os.environ.get("MI355X_BN_JOIN", "1") != "0")
+                out = _FusedBNFn.apply(
                     x, residual, self.weight, self.bias, self.running_mean,
                     self.running_var, self.momentum, self.eps, self.relu,
-                    self.num_batches_tracked)
+                    self.num_batches_tracked, join)
+                if not join:
+                    return out
+                # Residual layer = a block's output, which the next block
+                # reads twice (conv1 and identity / downsample). Callers
+                # still get ONE tensor; it carries a second autograd output
+                # over the same storage, and a block that feeds one path
+                # from each (models/resnet.py) gets its two gradients
+                # summed inside bn_bwd_reduce_join instead of by a
+                # stand-alone add kernel. A caller that ignores the twin
+                # behaves as before. The returned tensor is the view and
+                # holds the base, not the other way round: a base that held
+                # its own view would be a reference cycle through the
+                # view's base pointer and never be freed.
+                y, alias = out
+                setattr(alias, FusedBNReLU2d.JOIN_ATTR, y)
+                return alias
             if not (torch.is_grad_enabled() and
                     (x.requires_grad or self.weight.requires_grad)):
                 # inference: apply-only with running stats
