@@ -92,6 +92,23 @@ def main():
     t_stats_fin = timeit(lambda: _C.bn_fwd_finalize(
         part, mean, invstd, rm, rv, 0.1, 1e-5, rows, 64, True))
 
+    # --- wrw phase split, both kernels ("tr" = transposed LDS reads,
+    # "gather" = element gather): phase_mask 1 = band staging, 2 = dy
+    # staging, 4 = MFMA (on whatever the enabled stages left in LDS).
+    # Memset and cast launches are included in every figure (~10 us).
+    dyn = dy.permute(0, 2, 3, 1)
+    dw_out = torch.empty((64, 3, 7, 7), dtype=torch.bfloat16, device=dev,
+                         memory_format=torch.channels_last).permute(0, 2, 3, 1)
+    wscr = torch.empty(_C.stem_wrw_scratch(), dtype=torch.float32,
+                       device=dev)
+    wrw_phases = {}
+    for name, tr in (("tr", 1), ("gather", 0)):
+        wrw_phases[name] = {
+            label: round(timeit(
+                lambda: _C.stem_conv_wrw(xn, dyn, wscr, dw_out, mask, tr)), 1)
+            for label, mask in (("band", 1), ("dy", 2), ("band+dy", 3),
+                                ("mfma", 4), ("all", 7))}
+
     # numerics cross-check at this exact shape
     ref = F.conv2d(x.float(), wt.float(), None, 2, 3)
     got = _StemConvFn.apply(x, wt).float()
@@ -104,6 +121,7 @@ def main():
         "wrw_us": {"miopen": round(t_mio_wrw, 1), "mfma": round(t_wrw, 1),
                    "speedup": round(t_mio_wrw / t_wrw, 2)},
         "fwd_phase_us": phases,
+        "wrw_phase_us": wrw_phases,
         "stem_bn_stats_us": {"reduce+finalize": round(t_stats_sep, 1),
                              "finalize_on_conv_partial":
                                  round(t_stats_fin, 1)},

@@ -4,6 +4,7 @@
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
 #include <hip/hip_runtime.h>
+#include <cstdlib>
 
 extern "C" void launch_normalize_u8_to_bf16(
     const uint8_t* in, void* out, const float* scale_dev,
@@ -68,7 +69,9 @@ extern "C" int stem_fwd_stat_blocks(int Nb, int HO);
 extern "C" void launch_stem_conv_wrw(const void* x, const void* dy,
                                      float* dw_f32, void* dw_bf16,
                                      int Nb, int H, int W, int HO, int WO,
-                                     hipStream_t stream, int phase_mask);
+                                     hipStream_t stream, int phase_mask,
+                                     int tr);
+extern "C" int stem_wrw_scratch_elems();
 extern "C" void launch_conv3x3_wrw(const void* x, const void* dy,
                                    float* part, void* dw_bf16,
                                    int Nb, int H, int W, int C,
@@ -744,22 +747,39 @@ void stem_conv_fwd(torch::Tensor x, torch::Tensor w, torch::Tensor out,
 }
 
 // Weight grad: dw (bf16, weight layout) from x and dy; dw_f32 is the
-// [64][160] fp32 accumulation scratch.
+// fp32 accumulation scratch (stem_wrw_scratch() elements). ``tr``: 1 = the
+// transposed-LDS-read kernel, 0 = the element-gather kernel, -1 = ask
+// MI355X_STEM_WRW_TR (default 1), read on every call.
+int64_t stem_wrw_scratch() { return stem_wrw_scratch_elems(); }
+
 void stem_conv_wrw(torch::Tensor x, torch::Tensor dy, torch::Tensor dw_f32,
-                   torch::Tensor dw, int64_t phase_mask = 7) {
+                   torch::Tensor dw, int64_t phase_mask = 7,
+                   int64_t tr = -1) {
   TORCH_CHECK(x.is_cuda() && x.scalar_type() == torch::kBFloat16);
   TORCH_CHECK(dy.is_cuda() && dy.scalar_type() == torch::kBFloat16);
-  TORCH_CHECK(dw_f32.scalar_type() == torch::kFloat32 &&
-              dw_f32.numel() == 64 * 160);
+  TORCH_CHECK(dw_f32.is_cuda() && dw_f32.scalar_type() == torch::kFloat32 &&
+                  dw_f32.is_contiguous() &&
+                  dw_f32.numel() == stem_wrw_scratch(),
+              "dw_f32 must be fp32 [stem_wrw_scratch()]");
   TORCH_CHECK(dw.scalar_type() == torch::kBFloat16 &&
               dw.numel() == 64 * 7 * 7 * 3);
   int Nb = x.size(0), H = x.size(1), W = x.size(2);
   int HO = dy.size(1), WO = dy.size(2);
+  TORCH_CHECK(x.size(3) == 3 && dy.size(3) == 64, "stem is 3->64");
+  TORCH_CHECK(WO <= 128, "stem kernel handles output rows up to 128 px");
+  TORCH_CHECK(x.is_contiguous() && dy.is_contiguous() &&
+                  dy.size(0) == Nb && HO == (H - 1) / 2 + 1 &&
+                  WO == (W - 1) / 2 + 1,
+              "stem conv: dense NHWC x/dy with 7x7 s2 p3 geometry");
+  if (tr < 0) {
+    const char* e = std::getenv("MI355X_STEM_WRW_TR");
+    tr = !(e && e[0] == '0' && e[1] == 0);
+  }
   launch_stem_conv_wrw(x.data_ptr(), dy.data_ptr(),
                        dw_f32.data_ptr<float>(), dw.data_ptr(),
                        Nb, H, W, HO, WO,
                        at::cuda::getCurrentHIPStream().stream(),
-                       (int)phase_mask);
+                       (int)phase_mask, tr ? 1 : 0);
 }
 
 // 3x3/s1/p1 CxC weight grad: part fp32 [chunks][C][9][C] scratch
@@ -810,7 +830,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("stem_conv_wrw", &stem_conv_wrw,
         "MFMA stem conv weight-grad (fp32 accum + bf16 cast)",
         pybind11::arg("x"), pybind11::arg("dy"), pybind11::arg("dw_f32"),
-        pybind11::arg("dw"), pybind11::arg("phase_mask") = 7);
+        pybind11::arg("dw"), pybind11::arg("phase_mask") = 7,
+        pybind11::arg("tr") = -1);
+  m.def("stem_wrw_scratch", &stem_wrw_scratch,
+        "fp32 element count of the stem weight-grad accumulation scratch");
   m.def("normalize_u8_to_bf16", &normalize_u8_to_bf16,
         "fused uint8 NHWC -> normalized bf16 (same memory order)");
   m.def("groupfit_eval", &groupfit_eval,

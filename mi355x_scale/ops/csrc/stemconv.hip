@@ -27,6 +27,13 @@
 //       absorbs the K-padding taps), so there is no expansion phase and
 //       no bounds checks: the MFMA loop gathers its A-fragments straight
 //       from the band at koff(k) + px*6.
+//   wrw, r6: the element gather (56 two-byte LDS reads per 10 MFMAs) made
+//       LDS instruction issue the bound, at 1.57 TB/s and a fraction of
+//       the MFMA rate. stem_conv_wrw_kernel now reads both operands with
+//       ds_read_b64_tr_b16 (16 eight-byte reads per 12 MFMAs) from a band
+//       kept as two images 4 bytes out of phase, in a tap order of its
+//       own; 257 -> 133 us per step (profiles/r06_stem_wrw_tr_kernstats.md).
+//       The gather kernel stays as stem_conv_wrw_gather_kernel.
 #include <hip/hip_runtime.h>
 #include <hip/hip_bf16.h>
 
@@ -484,7 +491,9 @@ extern "C" __global__ __launch_bounds__(256, 3) void stem_conv_fwd_stats_kernel(
   }
 }
 
-// ---------------------------------------------------------------- wrw
+// ------------------------------------------------- wrw (element gather)
+// The first wrw kernel, kept selectable (MI355X_STEM_WRW_TR=0) for A/B
+// runs and as a second implementation the tests compare against.
 // block = 256 threads (4 waves) loops over ``rows_per_block`` output
 // rows; per row: band stage + dy-row stage, then each wave reduces ALL
 // four 32-px slices into its own (co, k) QUADRANT (2 co-subtiles x 5
@@ -494,7 +503,7 @@ extern "C" __global__ __launch_bounds__(256, 3) void stem_conv_fwd_stats_kernel(
 // Partials atomic-add into the L2-resident [CO][KPAD] fp32 tile once
 // per block (spread over 2.5k addresses — NOT the one-address-per-block
 // serialization the round-1 notes warn about).
-extern "C" __global__ __launch_bounds__(256) void stem_conv_wrw_kernel(
+extern "C" __global__ __launch_bounds__(256) void stem_conv_wrw_gather_kernel(
     const bf16* __restrict__ x,    // [N][H][W][CI]
     const bf16* __restrict__ dy,   // [N][HO][WO][CO]
     float* __restrict__ dw,        // [CO][KPAD] fp32 (pre-zeroed)
@@ -635,13 +644,319 @@ extern "C" __global__ __launch_bounds__(256) void stem_conv_wrw_kernel(
       }
 }
 
-// dw fp32 [CO][KPAD] -> bf16 grad in the conv weight's layout [CO][KTAP]
+// ------------------------------------------------ wrw (transposed reads)
+// The contraction index of this GEMM is the pixel, and the pixel is the
+// STRIDED index of both operands as they lie in LDS (dy is [px][co], the
+// band is [px*6 + tap]), so the kernel above builds every MFMA operand
+// from two-byte LDS reads: 56 of them plus packing per 10 MFMAs, and LDS
+// instruction issue is what it waits on. ds_read_b64_tr_b16 reads a
+// 4-row x 16-column block and hands each lane one column (4 K values in
+// one 8-byte read). What that needs, and how it is met here:
+//   * every lane address 8-byte aligned. Output pixels are 12 bytes apart
+//     in the band, so (a) the wrw has its own tap order
+//         k' = kh*24 + 3 + kw*3 + ci
+//     (a pixel's 24-tap window starts one input pixel early, at iw =
+//     2*px - 4, which is 8-byte aligned for even px; the three lead taps
+//     per kernel row multiply a neighbouring real pixel, finite garbage
+//     in dw columns the cast kernel never reads, so there is no
+//     zero-select; the same goes for columns 168..175 of the last
+//     tap-subtile, an eighth pseudo kernel row kh = 7: they read ring
+//     slot (ih0+7)&7, which holds the prologue zeros or the input row
+//     staged for the next output row, is in bounds and is only written
+//     behind the barrier), and (b) there are two band images 4 bytes out of
+//     phase: even pixels read the first, odd pixels the second;
+//   * K is contracted, so any pixel -> K-slot map works as long as A and
+//     B share it: K-group g (16 lanes) of read t takes the four pixels
+//     8g + ((g+t)&1) + {0,2,4,6} of the 32-px slice: one parity per
+//     block, and the eight dy rows one 32-lane half reads are distinct
+//     mod 8, which with 160-byte dy rows is conflict-free;
+//   * EXEC all ones at every transposed read: control flow around them is
+//     block- or wave-uniform (scalar branches), tails are padded with
+//     zeros (dy beyond WO) instead of masked.
+// Wave split: 4 co-subtiles x 11 tap-subtiles (176 >= 168); wave w takes
+// co-subtiles {2(w>>1), +1} and tap-subtiles 0..5 (w even) or 6..10 (w
+// odd): per slice 4 + 12 (10) eight-byte reads for 12 (10) MFMAs.
+// Row loop: the next row's dy slice AND its two new band rows are
+// prefetched into registers before the MFMA phase and written after it,
+// so a row costs one barrier pair; slices wholly beyond WO are skipped.
+// LDS: 2 band images (26,112 B) + one dy row (20,480 B) = 46,592 B ->
+// 3 blocks/CU, which the launch bounds also ask of the registers (154
+// VGPRs, no scratch; the gather kernel's 224 allowed 2).
+#define TRK 24                  // taps per kernel row in the wrw order
+#define KPADT 176               // 7*24 = 168 -> 11 sixteen-tap subtiles
+#define NKT (KPADT / 16)
+#define DYROW 80                // dy row stride (els): 160 B
+#define XTIMG (8 * XTROW)       // one band image (8 ring slots)
+#define XTODD (XTIMG + 2)       // odd-pixel image: same data, +4 bytes
+
+typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
+typedef __attribute__((ext_vector_type(4))) short s16x4;
+typedef __attribute__((ext_vector_type(8))) short s16x8;
+
+// one MFMA operand (8 K values per lane) from two transposed block reads
+__device__ __forceinline__ bf16x8 tr_frag(const bf16* p0, const bf16* p1) {
+  typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
+  const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)p0);
+  const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)p1);
+  const s16x8 v = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+  return __builtin_bit_cast(bf16x8, v);
+}
+
+// four band elements (chunk c of a row) into ring slot ``slot`` of both
+// images; the shifted image is only 4-byte aligned
+__device__ __forceinline__ void band_put(bf16* xt, int slot, int c,
+                                         bf16x4 v) {
+  bf16* e = xt + slot * XTROW + XTOFF + 4 * c;
+  *reinterpret_cast<bf16x4*>(e) = v;
+  const bf16x2 lo = {v[0], v[1]}, hi = {v[2], v[3]};
+  *reinterpret_cast<bf16x2*>(e + XTODD) = lo;
+  *reinterpret_cast<bf16x2*>(e + XTODD + 2) = hi;
+}
+
+// Stage input rows rfirst..6 of output row (n, ho) into their ring slots
+// (slot = ih & 7) of both images, zeros for rows outside the image.
+// Not pipelined: used for a block's first row, at image boundaries and
+// for row lengths that are no multiple of 4 elements.
+__device__ __forceinline__ void wrw_stage_rows(
+    const bf16* __restrict__ x, bf16* xt, int n, int ho, int rfirst,
+    int H, int W, int tid) {
+  const int rowlen = W * CI;
+  const int ih0 = ho * STRIDE - PADDING;
+  if ((rowlen & 3) == 0) {
+    const int nch = rowlen >> 2;
+    const int total = (KH - rfirst) * nch;
+    const bf16x4 z = {(bf16)0.0f, (bf16)0.0f, (bf16)0.0f, (bf16)0.0f};
+    for (int base = 0; base < total; base += 256 * 4) {
+      bf16x4 v[4];
+      int ss[4], cc[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const int i = base + tid + u * 256;
+        v[u] = z;
+        ss[u] = -1;
+        if (i < total) {
+          const int r = i / nch, c = i - r * nch;
+          const int ih = ih0 + rfirst + r;
+          ss[u] = ih & 7; cc[u] = c;
+          if (ih >= 0 && ih < H)
+            v[u] = reinterpret_cast<const bf16x4*>(
+                x + ((long long)n * H + ih) * rowlen)[c];
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < 4; ++u)
+        if (ss[u] >= 0) band_put(xt, ss[u], cc[u], v[u]);
+    }
+  } else {
+    for (int r = rfirst; r < KH; ++r) {
+      const int ih = ih0 + r;
+      const bool in = ih >= 0 && ih < H;
+      const bf16* src = x + ((long long)n * H + (in ? ih : 0)) * rowlen;
+      bf16* dst = xt + (ih & 7) * XTROW + XTOFF;
+      for (int i = tid; i < rowlen; i += 256) {
+        const bf16 v = in ? src[i] : (bf16)0.0f;
+        dst[i] = v;
+        dst[i + XTODD] = v;
+      }
+    }
+  }
+}
+
+extern "C" __global__ __launch_bounds__(256, 3) void stem_conv_wrw_kernel(
+    const bf16* __restrict__ x,    // [N][H][W][CI]
+    const bf16* __restrict__ dy,   // [N][HO][WO][CO]
+    float* __restrict__ dw,        // [CO][KPADT] fp32 (pre-zeroed), k' order
+    int Nb, int H, int W, int HO, int WO, int rows_per_block,
+    int phase_mask) {
+  __shared__ __attribute__((aligned(16))) bf16 xt[2 * XTIMG];
+  __shared__ __attribute__((aligned(16))) bf16 Dy[PXPAD * DYROW];
+  const int tid = threadIdx.x;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int lane = tid & 63;
+  const int l16 = lane & 15;
+  const int kgrp = lane >> 4;
+  const int q = l16 >> 2, p = l16 & 3;  // block row / 4-column group
+  const int nrows = Nb * HO;
+  const int mw = (wave >> 1) * 2;       // co-subtiles mw, mw+1
+  const int cw = (wave & 1) * 6;        // tap-subtiles cw .. cw+nk-1
+  const int nk = min(6, NKT - cw);
+  const int row0 = blockIdx.x * rows_per_block;
+  const int row_limit = min(row0 + rows_per_block, nrows);
+  if (row0 >= nrows) return;
+  const int rowlen = W * CI;
+  const bool vec = (rowlen & 3) == 0;
+  const int nchx = rowlen >> 2;         // 8-byte chunks per input row
+  const int nch = (WO * CO) >> 3;       // 16-byte chunks per dy row
+  const bf16x8 zv = {(bf16)0.0f, (bf16)0.0f, (bf16)0.0f, (bf16)0.0f,
+                     (bf16)0.0f, (bf16)0.0f, (bf16)0.0f, (bf16)0.0f};
+  const bf16x4 zx = {(bf16)0.0f, (bf16)0.0f, (bf16)0.0f, (bf16)0.0f};
+
+  f32x4 acc[2][6];
+#pragma unroll
+  for (int m = 0; m < 2; ++m)
+#pragma unroll
+    for (int c = 0; c < 6; ++c) acc[m][c] = (f32x4)0.0f;
+
+  // per-lane operand addressing. Read t (0/1) of K-group kgrp covers
+  // pixels 8*kgrp + ((kgrp+t)&1) + 2*q' (q' = 0..3); this lane supplies
+  // row q of the block, columns 4p..4p+3.
+  int aoff[2], boffpx[2];
+#pragma unroll
+  for (int t = 0; t < 2; ++t) {
+    const int par = (kgrp + t) & 1;
+    const int px = 8 * kgrp + par + 2 * q;
+    aoff[t] = px * DYROW + mw * 16 + 4 * p;
+    boffpx[t] = par * XTODD + px * (STRIDE * CI);
+  }
+  // tap-subtile c of this wave, columns 4p..4p+3: kernel row and offset
+  int khc[6], rc[6];
+#pragma unroll
+  for (int c = 0; c < 6; ++c) {
+    const int kq = (cw + c) * 16 + 4 * p;
+    khc[c] = kq / TRK;
+    rc[c] = kq - khc[c] * TRK;
+  }
+
+  // prologue: zero both images (pads stay zero for the whole block: the
+  // data region is overwritten with the same W every row), dy row 0
+  for (int i = tid; i < 2 * XTIMG / 8; i += 256)
+    reinterpret_cast<bf16x8*>(xt)[i] = zv;
+  {
+    const bf16x8* src = reinterpret_cast<const bf16x8*>(
+        dy + (long long)row0 * WO * CO);
+    bf16x8 v[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int i = tid + u * 256;
+      v[u] = (i < nch) ? src[i] : zv;
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int i = tid + u * 256;
+      *reinterpret_cast<bf16x8*>(Dy + (i >> 3) * DYROW + (i & 7) * 8) = v[u];
+    }
+  }
+  __syncthreads();
+  if (phase_mask & 1)
+    wrw_stage_rows(x, xt, row0 / HO, row0 % HO, 0, H, W, tid);
+  __syncthreads();
+
+  int n = row0 / HO;
+  int ho = row0 - n * HO;
+  for (int row = row0; row < row_limit; ++row) {
+    const bool have_next = row + 1 < row_limit;
+    const bool next_same = have_next && ho + 1 < HO;  // same image
+    // prefetch the next row's dy slice and (ring band) its two new input
+    // rows; the latency hides under the MFMA phase
+    bf16x8 v[4];
+    bf16x4 bv[2];
+    if (have_next && (phase_mask & 2)) {
+      const bf16x8* src = reinterpret_cast<const bf16x8*>(
+          dy + (long long)(row + 1) * WO * CO);
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const int i = tid + u * 256;
+        v[u] = (i < nch) ? src[i] : zv;
+      }
+    }
+    const int ihn = (ho + 1) * STRIDE - PADDING + (KH - STRIDE);
+    if (next_same && vec && (phase_mask & 1)) {
+#pragma unroll
+      for (int u = 0; u < 2; ++u) {
+        const int i = tid + u * 256;
+        const int r = i >= nchx ? 1 : 0;
+        const int c = i - r * nchx;
+        bv[u] = zx;
+        if (c < nchx && ihn + r < H)
+          bv[u] = reinterpret_cast<const bf16x4*>(
+              x + ((long long)n * H + ihn + r) * rowlen)[c];
+      }
+    }
+
+    if (phase_mask & 4) {
+      const int ih0 = ho * STRIDE - PADDING;
+      int boff[6];
+#pragma unroll
+      for (int c = 0; c < 6; ++c)
+        boff[c] = ((ih0 + khc[c]) & 7) * XTROW + rc[c];
+#pragma unroll
+      for (int sl = 0; sl < 4; ++sl) {
+        if (sl * 32 >= WO) break;  // block-uniform
+        bf16x8 af[2];
+#pragma unroll
+        for (int m = 0; m < 2; ++m)
+          af[m] = tr_frag(Dy + aoff[0] + sl * 32 * DYROW + m * 16,
+                          Dy + aoff[1] + sl * 32 * DYROW + m * 16);
+#pragma unroll
+        for (int c = 0; c < 6; ++c) {
+          if (c < nk) {  // wave-uniform
+            const int so = sl * 32 * STRIDE * CI;
+            const bf16x8 bfr = tr_frag(xt + boff[c] + boffpx[0] + so,
+                                       xt + boff[c] + boffpx[1] + so);
+#pragma unroll
+            for (int m = 0; m < 2; ++m)
+              acc[m][c] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+                  af[m], bfr, acc[m][c], 0, 0, 0);
+          }
+        }
+      }
+    }
+    if (!have_next) break;
+
+    __syncthreads();  // every wave is done reading this row's operands
+    if (phase_mask & 2) {
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const int i = tid + u * 256;
+        *reinterpret_cast<bf16x8*>(Dy + (i >> 3) * DYROW + (i & 7) * 8) =
+            v[u];
+      }
+    }
+    if (phase_mask & 1) {
+      if (!next_same) {
+        wrw_stage_rows(x, xt, n + 1, 0, 0, H, W, tid);
+      } else if (!vec) {
+        wrw_stage_rows(x, xt, n, ho + 1, KH - STRIDE, H, W, tid);
+      } else {
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+          const int i = tid + u * 256;
+          const int r = i >= nchx ? 1 : 0;
+          const int c = i - r * nchx;
+          if (c < nchx) band_put(xt, (ihn + r) & 7, c, bv[u]);
+        }
+      }
+    }
+    __syncthreads();
+    if (++ho == HO) { ho = 0; ++n; }
+  }
+
+  // D row = co (4*(lane>>4)+r), col = k' (c*16 + lane&15)
+#pragma unroll
+  for (int m = 0; m < 2; ++m)
+#pragma unroll
+    for (int c = 0; c < 6; ++c)
+      if (c < nk) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int co = (mw + m) * 16 + kgrp * 4 + r;
+          const int k = (cw + c) * 16 + l16;
+          atomicAdd(&dw[co * KPADT + k], acc[m][c][r]);
+        }
+      }
+}
+
+// dw fp32 -> bf16 grad in the conv weight's layout [CO][KTAP]; ``tr``:
+// dw is [CO][KPADT] in the transposed-read kernel's tap order k',
+// otherwise [CO][KPAD] in weight order
 extern "C" __global__ __launch_bounds__(256) void stem_wrw_cast_kernel(
-    const float* __restrict__ dw, bf16* __restrict__ out) {
+    const float* __restrict__ dw, bf16* __restrict__ out, int tr) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i < CO * KTAP) {
     const int co = i / KTAP, k = i - co * KTAP;
-    out[i] = (bf16)dw[co * KPAD + k];
+    const int kh = k / (KW * CI);
+    out[i] = (bf16)(tr ? dw[co * KPADT + k + kh * (TRK - KW * CI) + 3]
+                       : dw[co * KPAD + k]);
   }
 }
 
@@ -677,16 +992,24 @@ extern "C" void launch_stem_conv_wrw(const void* x, const void* dy,
                                      float* dw_f32, void* dw_bf16,
                                      int Nb, int H, int W, int HO, int WO,
                                      hipStream_t stream,
-                                     int phase_mask = 7) {
+                                     int phase_mask, int tr) {
   const int nrows = Nb * HO;
   const int target_blocks = 768;
   const int rpb = (nrows + target_blocks - 1) / target_blocks;
   const int blocks = (nrows + rpb - 1) / rpb;
-  hipMemsetAsync(dw_f32, 0, CO * KPAD * sizeof(float), stream);
-  hipLaunchKernelGGL(stem_conv_wrw_kernel, dim3(blocks), dim3(256), 0,
-                     stream, (const bf16*)x, (const bf16*)dy, dw_f32,
-                     Nb, H, W, HO, WO, rpb, phase_mask);
+  (void)hipMemsetAsync(dw_f32, 0, CO * KPADT * sizeof(float), stream);
+  if (tr)
+    hipLaunchKernelGGL(stem_conv_wrw_kernel, dim3(blocks), dim3(256), 0,
+                       stream, (const bf16*)x, (const bf16*)dy, dw_f32,
+                       Nb, H, W, HO, WO, rpb, phase_mask);
+  else
+    hipLaunchKernelGGL(stem_conv_wrw_gather_kernel, dim3(blocks), dim3(256),
+                       0, stream, (const bf16*)x, (const bf16*)dy, dw_f32,
+                       Nb, H, W, HO, WO, rpb, phase_mask);
   hipLaunchKernelGGL(stem_wrw_cast_kernel,
                      dim3((CO * KTAP + 255) / 256), dim3(256), 0, stream,
-                     dw_f32, (bf16*)dw_bf16);
+                     dw_f32, (bf16*)dw_bf16, tr);
 }
+
+// fp32 elements of the wrw accumulation scratch (either kernel)
+extern "C" int stem_wrw_scratch_elems() { return CO * KPADT; }

@@ -6,9 +6,13 @@ forward + ~294 us weight-grad per step at bs 212 on the flagship bench,
 ~7% of the whole step. ``ops/csrc/stemconv.hip`` computes it as the
 GEMM it is on ``v_mfma_f32_16x16x32_bf16`` with a pixel-padded LDS
 input band per output row: forward 210 us (1.73x MIOpen, padded
-weights read from L1-resident global), weight-grad 267 us (1.12x;
-ring-band staging + a software-pipelined dy stage prefetched into
-registers under the MFMA phase).
+weights read from L1-resident global), weight-grad 133 us per step
+(2.1x MIOpen in ``benchmarks/bench_stemconv.py``; ring-band staging,
+the next row's dy slice and band rows prefetched into registers under
+the MFMA phase, and both MFMA operands read from LDS with the
+transposing ``ds_read_b64_tr_b16``). ``MI355X_STEM_WRW_TR=0``, read by
+the extension on every call, selects the earlier weight-grad kernel
+that gathers its operands element by element (260 us; A/B runs, tests).
 
 The default forward kernel (``MI355X_STEM_FUSED_STATS``, ``0`` = the
 one-row-per-block kernel above) gives a block eight output rows: the
@@ -71,7 +75,9 @@ def _stem_backward(ctx, dy: torch.Tensor):
         dy = dy.to(torch.bfloat16)
     dy = dy.contiguous(memory_format=torch.channels_last)
     dw = torch.empty_like(weight)
-    scratch = torch.empty(64 * 160, dtype=torch.float32,
+    # which wrw kernel runs is the extension's choice per call
+    # (MI355X_STEM_WRW_TR, "0" = the element-gather kernel)
+    scratch = torch.empty(_C.stem_wrw_scratch(), dtype=torch.float32,
                           device=x.device)
     _C.stem_conv_wrw(x.permute(0, 2, 3, 1), dy.permute(0, 2, 3, 1),
                      scratch, dw.permute(0, 2, 3, 1))
@@ -121,7 +127,8 @@ class StemConv2d(nn.Conv2d):
         from . import HAVE_EXT
         return (HAVE_EXT and x.is_cuda
                 and os.environ.get("MI355X_STEM_CONV", "1") == "1"
-                and x.shape[-1] <= 262  # kernel's 128-px output-row cap
+                # the kernels' cap is 128 OUTPUT pixels per row
+                and (x.shape[-1] - 1) // 2 + 1 <= 128
                 and x.dtype == torch.bfloat16
                 and self.weight.dtype == torch.bfloat16
                 and x.is_contiguous(memory_format=torch.channels_last)

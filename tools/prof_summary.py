@@ -30,7 +30,8 @@ def summarize(root: str, limit: int = 40, window_ms: float = 0.0):
         print(f"steady-state window: last {window_ms:.0f} ms\n")
     q = f'''
     select ks.display_name, count(*), sum(k."end" - k.start)/1e6,
-           avg(k."end" - k.start)/1e3
+           avg(k."end" - k.start)/1e3, min(k."end" - k.start)/1e3,
+           max(k."end" - k.start)/1e3
     from rocpd_kernel_dispatch_{sfx} k
     join rocpd_info_kernel_symbol_{sfx} ks on k.kernel_id = ks.id
     {where}
@@ -38,11 +39,11 @@ def summarize(root: str, limit: int = 40, window_ms: float = 0.0):
     '''
     rows = list(con.execute(q))
     tot = sum(r[2] for r in rows)
-    print(f"| kernel | calls | total_ms | avg_us | % |")
-    print(f"|---|---|---|---|---|")
-    for name, n, ms, avg in rows[:limit]:
-        print(f"| {name[:78]} | {n} | {ms:.2f} | {avg:.1f} "
-              f"| {100 * ms / tot:.1f} |")
+    print(f"| kernel | calls | total_ms | avg_us | min_us | max_us | % |")
+    print(f"|---|---|---|---|---|---|---|")
+    for name, n, ms, avg, lo, hi in rows[:limit]:
+        print(f"| {name[:78]} | {n} | {ms:.2f} | {avg:.1f} | {lo:.1f} "
+              f"| {hi:.1f} | {100 * ms / tot:.1f} |")
     print(f"\ntotal kernel time: {tot:.1f} ms over "
           f"{sum(r[1] for r in rows)} dispatches")
 
