@@ -147,6 +147,46 @@ def run_fine_grained_forecast_gpu(demand_df: pd.DataFrame,
     return res[["Product", "SKU", "Date", "Demand", "Demand_Fitted"]]
 
 
+def run_holtwinters_forecast_gpu(demand_df: pd.DataFrame,
+                                 trend: Optional[str] = "add",
+                                 damped_trend: bool = False,
+                                 seasonal: Optional[str] = None,
+                                 seasonal_periods: Optional[int] = None,
+                                 forecast_steps: int = 0) -> pd.DataFrame:
+    """Holt-Winters for every (Product, SKU) group on the batched GPU fit
+    (the reference's single-series walkthrough, ref :143-188, at panel
+    scale). Returns the TUNING_SCHEMA columns with one-step-ahead fitted
+    demand; with ``forecast_steps > 0`` each group gets that many future
+    rows appended (dates continue at the spacing of the last two, Demand
+    is NaN, Demand_Fitted holds the forecast).
+    """
+    from ..groupby.gather import long_from_panel, panel_from_long
+    from .batched_hw import batched_hw_fit_gpu
+    y, gindex, dates = panel_from_long(demand_df, ["Product", "SKU"],
+                                       "Date", "Demand")
+    H = int(forecast_steps)
+    out = batched_hw_fit_gpu(y, trend=trend, damped_trend=damped_trend,
+                             seasonal=seasonal,
+                             seasonal_periods=seasonal_periods,
+                             forecast_steps=H)
+    demand = y.astype(np.float64)
+    fitted = out["fitted"].cpu().numpy().astype(np.float64)
+    if H > 0:
+        d = pd.DatetimeIndex(pd.to_datetime(dates))
+        future = d[-1] + (d[-1] - d[-2]) * np.arange(1, H + 1)
+        dates = d.append(pd.DatetimeIndex(future)).to_numpy()
+        demand = np.concatenate(
+            [demand, np.full((len(demand), H), np.nan)], axis=1)
+        fitted = np.concatenate(
+            [fitted, out["forecast"].cpu().numpy().astype(np.float64)],
+            axis=1)
+    res = long_from_panel(demand, gindex, dates, ["Product", "SKU"], "Date",
+                          [("Demand", demand), ("Demand_Fitted", fitted)])
+    if not np.issubdtype(res["Date"].dtype, np.datetime64):
+        res["Date"] = pd.to_datetime(res["Date"])
+    return res[["Product", "SKU", "Date", "Demand", "Demand_Fitted"]]
+
+
 def _shard_of(product: str, sku: str, num_shards: int) -> int:
     """Deterministic group→shard assignment (stable across processes —
     md5, not the salted builtin hash)."""

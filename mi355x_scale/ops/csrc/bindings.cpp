@@ -3,6 +3,7 @@
 
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
+#include <c10/hip/HIPException.h>
 #include <hip/hip_runtime.h>
 #include <cstdlib>
 
@@ -143,6 +144,100 @@ void groupfit_final(torch::Tensor yT, torch::Tensor xc0, torch::Tensor xc1,
       status.data_ptr<uint8_t>(),
       fp(b0), fp(b1), fp(b2), fp(w0), fp(w1), fp(w2),
       T, G, (int)xc0.size(1), stream.stream());
+}
+
+extern "C" int launch_hwfit_search(const float* yT, const float* table,
+                                   float* params, float* sse,
+                                   unsigned char* statusv, int T,
+                                   long long G, int C, int trend, int seas,
+                                   int m, int waves_req,
+                                   hipStream_t stream);
+extern "C" void launch_hwfit_final(const float* yT, const float* params,
+                                   float* fitted, float* forecast,
+                                   float* level, float* trendv,
+                                   float* season, float* sse,
+                                   unsigned char* statusv, int T,
+                                   long long G, int trend, int seas, int m,
+                                   int H, hipStream_t stream);
+
+static void _check_hw_model(const torch::Tensor& yT, int64_t seas,
+                            int64_t m) {
+  _check_f32(yT, "yT");
+  TORCH_CHECK(yT.dim() == 2 && yT.size(0) >= 2 && yT.size(1) >= 1,
+              "yT must be [T>=2][G>=1]");
+  TORCH_CHECK(yT.size(0) <= (1 << 24), "series too long");
+  TORCH_CHECK(seas >= 0 && seas <= 2, "seasonal mode must be 0, 1 or 2");
+  TORCH_CHECK(seas ? (m >= 2 && m <= 64) : m == 1,
+              "seasonal_periods must be in [2, 64] (1 without a season)");
+}
+
+static void _check_hw_vec(const torch::Tensor& t, int64_t rows, int64_t G,
+                          const char* name) {
+  _check_f32(t, name);
+  TORCH_CHECK(t.numel() == rows * G, name, " has the wrong size");
+}
+
+// Holt-Winters grid + refinement search. yT: [T][G]; table: [C][4]
+// (alpha, beta, gamma, phi) in product order; params: [G][4] out; sse [G]
+// out; status [G] u8 out. Returns the waves per block it ran with.
+int64_t hwfit_search(torch::Tensor yT, torch::Tensor table,
+                     torch::Tensor params, torch::Tensor sse,
+                     torch::Tensor status, bool trend, int64_t seas,
+                     int64_t m, int64_t waves) {
+  _check_hw_model(yT, seas, m);
+  const int64_t G = yT.size(1);
+  _check_f32(table, "table");
+  TORCH_CHECK(table.dim() == 2 && table.size(1) == 4 && table.size(0) >= 1,
+              "table must be [C>=1][4]");
+  _check_hw_vec(params, 4, G, "params");
+  _check_hw_vec(sse, 1, G, "sse");
+  TORCH_CHECK(status.scalar_type() == torch::kUInt8 && status.is_cuda() &&
+              status.is_contiguous() && status.numel() == G,
+              "status must be [G] u8 on GPU");
+  TORCH_CHECK(waves >= 0 && waves <= 16, "waves must be in [0, 16]");
+  auto stream = at::cuda::getCurrentHIPStream();
+  const int nw = launch_hwfit_search(
+      yT.data_ptr<float>(), table.data_ptr<float>(),
+      params.data_ptr<float>(), sse.data_ptr<float>(),
+      status.data_ptr<uint8_t>(), (int)yT.size(0), (long long)G,
+      (int)table.size(0), trend ? 1 : 0, (int)seas, (int)m, (int)waves,
+      stream.stream());
+  C10_HIP_KERNEL_LAUNCH_CHECK();
+  return nw;
+}
+
+// Holt-Winters final pass at given per-group parameters. fitted [T][G],
+// forecast [H][G], level/trend/sse [G], season [m][G], status [G] u8.
+void hwfit_final(torch::Tensor yT, torch::Tensor params,
+                 torch::Tensor fitted, torch::Tensor forecast,
+                 torch::Tensor level, torch::Tensor trendv,
+                 torch::Tensor season, torch::Tensor sse,
+                 torch::Tensor status, bool trend, int64_t seas,
+                 int64_t m) {
+  _check_hw_model(yT, seas, m);
+  const int64_t T = yT.size(0), G = yT.size(1);
+  _check_hw_vec(params, 4, G, "params");
+  _check_hw_vec(fitted, T, G, "fitted");
+  TORCH_CHECK(forecast.is_cuda() &&
+              forecast.scalar_type() == torch::kFloat32 &&
+              forecast.is_contiguous() && forecast.dim() == 2 &&
+              forecast.size(1) == G, "forecast must be [H][G] f32 on GPU");
+  _check_hw_vec(level, 1, G, "level");
+  _check_hw_vec(trendv, 1, G, "trend");
+  _check_hw_vec(season, m, G, "season");
+  _check_hw_vec(sse, 1, G, "sse");
+  TORCH_CHECK(status.scalar_type() == torch::kUInt8 && status.is_cuda() &&
+              status.is_contiguous() && status.numel() == G,
+              "status must be [G] u8 on GPU");
+  auto stream = at::cuda::getCurrentHIPStream();
+  launch_hwfit_final(
+      yT.data_ptr<float>(), params.data_ptr<float>(),
+      fitted.data_ptr<float>(), forecast.data_ptr<float>(),
+      level.data_ptr<float>(), trendv.data_ptr<float>(),
+      season.data_ptr<float>(), sse.data_ptr<float>(),
+      status.data_ptr<uint8_t>(), (int)T, (long long)G, trend ? 1 : 0,
+      (int)seas, (int)m, (int)forecast.size(0), stream.stream());
+  C10_HIP_KERNEL_LAUNCH_CHECK();
 }
 
 // Wc [n][G], wm [G] from the time-major panel (differenced d times,
@@ -840,6 +935,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "batched per-group ARIMAX candidate evaluation (validation MSE)");
   m.def("groupfit_final", &groupfit_final,
         "batched per-group final fit (fitted values + params)");
+  m.def("hwfit_search", &hwfit_search,
+        "batched Holt-Winters grid + refinement search (params, sse)",
+        pybind11::arg("yT"), pybind11::arg("table"), pybind11::arg("params"),
+        pybind11::arg("sse"), pybind11::arg("status"),
+        pybind11::arg("trend"), pybind11::arg("seas"), pybind11::arg("m"),
+        pybind11::arg("waves") = 0);
+  m.def("hwfit_final", &hwfit_final,
+        "batched Holt-Winters final pass (fitted, state, forecast)");
   m.def("diff_center", &diff_center,
         "difference + per-group centering of the time-major panel");
   m.def("exog_project_mfma", &exog_project_mfma,

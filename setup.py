@@ -17,6 +17,7 @@ SRC = [
     "mi355x_scale/ops/csrc/bindings.cpp",
     "mi355x_scale/ops/csrc/preprocess.hip",
     "mi355x_scale/ops/csrc/groupfit.hip",
+    "mi355x_scale/ops/csrc/hwfit.hip",
     "mi355x_scale/ops/csrc/mfma_project.hip",
     "mi355x_scale/ops/csrc/fused_bn.hip",
     "mi355x_scale/ops/csrc/adam.hip",

@@ -1,0 +1,333 @@
+"""Batched Holt-Winters: the numpy oracle against the scalar class (CPU)
+and the HIP kernels against the oracle (GPU).
+
+Data is the project generator panel ``generate_demand_data(5, 26, 157)``
+(130 groups = two full waves + a 2-lane tail, positive values so ``mul``
+is well defined); short series are its leading columns.
+
+The GPU tolerances are not fitted to the kernel: they come from running
+the oracle in float32 against float64 on this same data on the CPU (worst
+SSE deviation 1.1e-5 relative at T >= 7, worst fitted/state deviation
+6.3e-6 of mean|y|) with a ~10x margin for FMA contraction, a different
+summation order in the initial means, and division rounding.
+"""
+import functools
+
+import numpy as np
+import pytest
+
+from mi355x_scale.data.generator import generate_demand_data
+from mi355x_scale.forecast import ExponentialSmoothing
+from mi355x_scale.forecast.batched_hw import (batched_hw_fit_gpu,
+                                              batched_hw_reference,
+                                              candidate_table)
+
+H = 40
+VARIANTS = {
+    "simple": dict(),
+    "trend": dict(trend="add"),
+    "damped": dict(trend="add", damped_trend=True),
+    "trend_add4": dict(trend="add", seasonal="add", seasonal_periods=4),
+    "damped_mul4": dict(trend="add", damped_trend=True, seasonal="mul",
+                        seasonal_periods=4),
+    "trend_add52": dict(trend="add", seasonal="add", seasonal_periods=52),
+    "trend_mul52": dict(trend="add", seasonal="mul", seasonal_periods=52),
+    "trend_add64": dict(trend="add", seasonal="add", seasonal_periods=64),
+}
+SEVEN = ["simple", "trend", "damped", "trend_add4", "damped_mul4",
+         "trend_add52", "trend_mul52"]
+SHORT_VARIANTS = ["simple", "trend", "damped", "trend_add4", "damped_mul4"]
+FIXED_CASES = ([(v, 157) for v in SEVEN] + [("trend_add64", 157)]
+               + [(v, T) for v in SHORT_VARIANTS for T in (2, 7, 8, 9)])
+SEARCH_CASES = ([(v, 157) for v in SEVEN]
+                + [(v, T) for v in SHORT_VARIANTS for T in (7, 8, 9)])
+
+
+@functools.lru_cache(maxsize=None)
+def _panel():
+    df = generate_demand_data(5, 26, 157)
+    y = df.pivot_table(index=["Product", "SKU"], columns="Date",
+                       values="Demand").to_numpy(dtype=np.float64)
+    assert y.shape == (130, 157) and (y > 0).all()
+    y.setflags(write=False)
+    return y
+
+
+@functools.lru_cache(maxsize=None)
+def _oracle(variant, T):
+    """f64 oracle search + final on all 130 groups; computed once per
+    case and shared (read-only) by the fixed-params and search tests."""
+    out = batched_hw_reference(_panel()[:, :T], forecast_steps=H,
+                               **VARIANTS[variant])
+    for v in out.values():
+        v.setflags(write=False)
+    return out
+
+
+def _scalar_params(res):
+    return np.array([res.params[k] for k in (
+        "smoothing_level", "smoothing_trend", "smoothing_seasonal",
+        "damping_trend")])
+
+
+# ------------------------------------------------------------------ CPU
+@pytest.mark.parametrize("variant,T", [(v, 157) for v in SEVEN]
+                         + [("trend_add4", T) for T in (9, 8, 7)])
+def test_oracle_equals_scalar_class(variant, T):
+    """T = 8 and 7 straddle the n >= 2m initialisation switch at m = 4."""
+    kw = VARIANTS[variant]
+    y = _panel()[:3, :T]
+    out = batched_hw_reference(y, forecast_steps=H, **kw)
+    assert out["status"].tolist() == [1, 1, 1]
+    for g in range(3):
+        res = ExponentialSmoothing(y[g], **kw).fit()
+        np.testing.assert_allclose(out["params"][g], _scalar_params(res),
+                                   rtol=0, atol=1e-12)
+        np.testing.assert_allclose(out["sse"][g], res.sse, rtol=1e-9)
+        np.testing.assert_allclose(out["fitted"][g], res.fittedvalues,
+                                   rtol=1e-9)
+        np.testing.assert_allclose(out["forecast"][g], res.forecast(H),
+                                   rtol=1e-9)
+
+
+def test_oracle_fixed_params_skip_the_search():
+    y = _panel()[:4]
+    kw = VARIANTS["trend_add4"]
+    one = batched_hw_reference(y, params=(0.3, 0.1, 0.2, 1.0), **kw)
+    assert np.array_equal(one["params"], np.tile([0.3, 0.1, 0.2, 1.0],
+                                                 (4, 1)))
+    res = ExponentialSmoothing(y[2], **kw).fit(
+        smoothing_level=0.3, smoothing_trend=0.1, smoothing_seasonal=0.2,
+        damping_trend=1.0, optimized=False)
+    # the scalar class still refines (alpha, beta); the oracle must not
+    per = batched_hw_reference(y, params=np.tile(_scalar_params(res),
+                                                 (4, 1)), **kw)
+    np.testing.assert_allclose(per["sse"][2], res.sse, rtol=1e-9)
+    assert one["season"].shape == (4, 4) and one["forecast"].shape == (4, 0)
+
+
+@pytest.mark.parametrize("kw", [
+    dict(trend="mul"),
+    dict(seasonal="additive", seasonal_periods=4),
+    dict(seasonal="add"),
+    dict(seasonal="add", seasonal_periods=1),
+    dict(seasonal="mul", seasonal_periods=65),
+])
+def test_validation_raises(kw):
+    with pytest.raises(ValueError):
+        batched_hw_reference(_panel()[:2], **kw)
+
+
+def test_validation_raises_on_short_series():
+    with pytest.raises(ValueError):
+        batched_hw_reference(_panel()[:2, :1], trend="add")
+
+
+@pytest.mark.parametrize("variant", ["trend_add4", "damped_mul4"])
+def test_non_finite_series_fails_alone(variant):
+    kw = VARIANTS[variant]
+    y = _panel()[:3].copy()
+    y[1, 10] = np.nan
+    out = batched_hw_reference(y, forecast_steps=H, **kw)
+    assert out["status"].tolist() == [1, 0, 1]
+    for k in ("params", "sse", "fitted", "level", "trend", "season",
+              "forecast"):
+        assert np.isnan(out[k][1]).all(), k
+    for g in (0, 2):
+        alone = batched_hw_reference(y[g:g + 1], forecast_steps=H, **kw)
+        for k in alone:
+            assert np.array_equal(out[k][g], alone[k][0]), (g, k)
+
+
+def test_candidate_table_is_product_order():
+    t = candidate_table("add", True, "mul")
+    assert t.shape == (7 * 7 * 7 * 3, 4)
+    assert t[0].tolist() == [0.05, 0.05, 0.05, 0.8]
+    assert t[1].tolist() == [0.05, 0.05, 0.05, 0.9]
+    assert t[3].tolist() == [0.05, 0.05, 0.1, 0.8]
+    assert candidate_table(None, False, None).shape == (7, 4)
+
+
+# ------------------------------------------------------------------ GPU
+def _np(out):
+    return {k: v.cpu().numpy() for k, v in out.items()}
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("variant,T", FIXED_CASES)
+def test_gpu_fixed_params_match_oracle(variant, T):
+    """hwfit_final at the oracle's parameters — no argmin involved.
+
+    Bounds: SSE 1e-4 relative (T = 2, where the SSE is ~0: 1e-4 x
+    mean|y|^2 absolute); fitted / forecast / level / additive season
+    1e-4 x mean|y| of the group; trend and multiplicative season 1e-4
+    absolute.
+
+    Measured on an MI355X, worst over all 28 cases, in the units of each
+    bound: SSE 1.3e-7 (T = 2: 8.4e-10), fitted 8.7e-8, forecast 1.2e-6,
+    level 6.5e-8, additive season 3.0e-8, multiplicative season 6.9e-8,
+    trend 7.7e-6. The final pass runs in double for the trend's sake: an
+    all-f32 pass (and the f32 CPU emulation alike) reaches 1.2e-4..1.7e-4
+    absolute on the trend at T = 7..9, where beta ~ 0.99 makes it the
+    difference of two levels near 1000 (f32 ulp 6e-5..1.2e-4).
+    """
+    kw = VARIANTS[variant]
+    ref = _oracle(variant, T)
+    y = _panel()[:, :T]
+    got = _np(batched_hw_fit_gpu(y, params=ref["params"], forecast_steps=H,
+                                 **kw))
+    assert got["status"].tolist() == [1] * 130
+    scale = np.abs(y).mean(axis=1)
+    mul = kw.get("seasonal") == "mul"
+    np.testing.assert_allclose(got["params"], ref["params"], atol=1e-6)
+    if T == 2:
+        d_sse = np.abs(got["sse"] - ref["sse"]) / scale ** 2
+    else:
+        d_sse = np.abs(got["sse"] - ref["sse"]) / ref["sse"]
+    dev = {"sse": d_sse.max()}
+    for k in ("fitted", "forecast", "level", "season"):
+        d = np.abs(got[k] - ref[k])
+        if not (k == "season" and mul):
+            d = d / (scale[:, None] if d.ndim == 2 else scale)
+        dev[k] = d.max()
+    dev["trend"] = np.abs(got["trend"] - ref["trend"]).max()
+    print(f"hwfit_final {variant} T={T}: "
+          + " ".join(f"{k}={v:.3g}" for k, v in dev.items()))
+    for k, v in dev.items():
+        assert v <= 1e-4, (k, v)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("variant,T", SEARCH_CASES)
+def test_gpu_search_matches_oracle(variant, T):
+    """(a) the kernel's parameters, re-scored in f64, are within 1e-4 of
+    the oracle's best SSE; (b) they equal the oracle's to 1e-6 in >= 95%
+    of the groups (near-ties may flip in f32).
+
+    Measured on an MI355X: regret at most 9.2e-8; agreement 100% on every
+    case except damped+mul m=4 at T = 8 (99.2%, one group of 130)."""
+    kw = VARIANTS[variant]
+    ref = _oracle(variant, T)
+    y = _panel()[:, :T]
+    got = _np(batched_hw_fit_gpu(y, forecast_steps=H, **kw))
+    assert got["status"].tolist() == [1] * 130
+    rescored = batched_hw_reference(
+        y, params=got["params"].astype(np.float64), **kw)["sse"]
+    regret = (rescored / ref["sse"] - 1.0).max()
+    same = (np.abs(got["params"] - ref["params"]).max(axis=1) <= 1e-6)
+    print(f"hwfit_search {variant} T={T}: regret={regret:.3g} "
+          f"agree={same.mean():.4f}")
+    assert (rescored <= ref["sse"] * (1 + 1e-4)).all(), regret
+    assert same.mean() >= 0.95, same.mean()
+
+
+def _raw_fit(y, kw, pad=64):
+    """search + final straight through the extension, every output
+    buffer followed by ``pad`` canary elements."""
+    import torch
+    from mi355x_scale.forecast.batched import _to_yT
+    from mi355x_scale.ops import _C
+    G, T = y.shape
+    m = kw.get("seasonal_periods") or 1
+    seas = {None: 0, "add": 1, "mul": 2}[kw.get("seasonal")]
+    trend = kw.get("trend") is not None
+    yT = _to_yT(y, "cuda")
+    bufs = {}
+
+    def out(name, shape, dtype=torch.float32):
+        n = int(np.prod(shape))
+        canary = 173 if dtype == torch.uint8 else -12345.0
+        full = torch.full((n + pad,), canary, dtype=dtype, device="cuda")
+        bufs[name] = (full, n, canary)
+        return full[:n].view(shape)
+
+    table = torch.tensor(
+        candidate_table(kw.get("trend"), kw.get("damped_trend", False),
+                        kw.get("seasonal")),
+        dtype=torch.float32, device="cuda")
+    par = out("params", (G, 4))
+    _C.hwfit_search(yT, table, par, out("search_sse", (G,)),
+                    out("search_status", (G,), torch.uint8), trend, seas,
+                    m, 0)
+    res = {"params": par,
+           "fitted": out("fitted", (T, G)), "forecast": out("forecast", (H, G)),
+           "level": out("level", (G,)), "trend": out("trend", (G,)),
+           "season": out("season", (m, G)), "sse": out("sse", (G,)),
+           "status": out("status", (G,), torch.uint8)}
+    _C.hwfit_final(yT, par, res["fitted"], res["forecast"], res["level"],
+                   res["trend"], res["season"], res["sse"], res["status"],
+                   trend, seas, m)
+    torch.cuda.synchronize()
+    for name, (full, n, canary) in bufs.items():
+        assert (full[n:] == canary).all().item(), f"canary after {name}"
+    for k in ("fitted", "forecast", "season"):
+        res[k] = res[k].t()
+    return _np(res)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("G", [1, 63, 65])
+def test_gpu_grid_tail_is_bit_exact_and_in_bounds(G):
+    kw = VARIANTS["trend_add52"]
+    y = _panel()
+    full = _np(batched_hw_fit_gpu(y, forecast_steps=H, **kw))
+    part = _raw_fit(y[:G], kw)
+    for k in full:
+        assert np.array_equal(part[k], full[k][:G]), k
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("variant", ["damped_mul4", "trend_add52"])
+def test_gpu_candidate_split_invariance(variant):
+    """Splitting the candidate list over 1, 3 or the default number of
+    waves per block picks the same winner with the same SSE, bit for
+    bit."""
+    kw = VARIANTS[variant]
+    y = _panel()
+    runs = [_np(batched_hw_fit_gpu(y, search_waves=w, **kw))
+            for w in (0, 1, 3)]
+    for r in runs[1:]:
+        assert np.array_equal(r["params"], runs[0]["params"])
+        assert np.array_equal(r["sse"], runs[0]["sse"])
+
+
+@pytest.mark.gpu
+def test_gpu_non_finite_series_fails_alone():
+    kw = VARIANTS["trend_add4"]
+    y = _panel()[:70].copy()
+    y[65, 10] = np.nan
+    got = _np(batched_hw_fit_gpu(y, forecast_steps=H, **kw))
+    clean = _np(batched_hw_fit_gpu(_panel()[:70], forecast_steps=H, **kw))
+    assert got["status"][65] == 0 and got["status"].sum() == 69
+    keep = np.arange(70) != 65
+    for k in got:
+        if k != "status":
+            assert np.isnan(got[k][65]).all(), k
+        assert np.array_equal(got[k][keep], clean[k][keep]), k
+
+
+@pytest.mark.gpu
+def test_gpu_pipeline_appends_forecast_rows():
+    import pandas as pd
+    from mi355x_scale.forecast import run_holtwinters_forecast_gpu
+    df = generate_demand_data(2, 5, 157)
+    res = run_holtwinters_forecast_gpu(df, seasonal="add",
+                                       seasonal_periods=52,
+                                       forecast_steps=H)
+    assert list(res.columns) == ["Product", "SKU", "Date", "Demand",
+                                 "Demand_Fitted"]
+    assert len(res) == 10 * 197
+    n_groups = 0
+    for _, grp in res.groupby(["Product", "SKU"], observed=True):
+        n_groups += 1
+        assert len(grp) == 197
+        steps = grp["Date"].diff().dropna()
+        assert (steps == pd.Timedelta(weeks=1)).all()
+        past, future = grp.iloc[:157], grp.iloc[157:]
+        assert past["Demand"].notna().all()
+        assert future["Demand"].isna().all()
+        assert np.isfinite(grp["Demand_Fitted"].to_numpy()).all()
+        tail = past.iloc[52:]
+        mse = np.mean((tail["Demand"] - tail["Demand_Fitted"]) ** 2)
+        assert mse < past["Demand"].var()
+    assert n_groups == 10
