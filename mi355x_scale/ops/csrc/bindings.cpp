@@ -86,6 +86,18 @@ static void _check_f32(const torch::Tensor& t, const char* name) {
               name, " must be contiguous f32 on GPU");
 }
 
+// Optional f32 vector: an empty tensor means "not given".
+static const float* _f32_or_null(const torch::Tensor& t) {
+  return t.numel() ? t.data_ptr<float>() : nullptr;
+}
+
+// u8 max-pool window codes.
+static void _check_code(const torch::Tensor& code) {
+  TORCH_CHECK(code.scalar_type() == torch::kUInt8 && code.is_cuda() &&
+                  code.is_contiguous(),
+              "code must be contiguous u8 on GPU");
+}
+
 // yT: [T][G] time-major; xc{d}: [T-d][KX]; pj{d}: [KX][S-d];
 // orders: [C][3] i32; mse: [C][G] f32 out; status: [C][G] u8 out
 void groupfit_eval(torch::Tensor yT, torch::Tensor xc0, torch::Tensor xc1,
@@ -105,15 +117,13 @@ void groupfit_eval(torch::Tensor yT, torch::Tensor xc0, torch::Tensor xc1,
   TORCH_CHECK(S > 8 && S <= T, "need 8 < S <= T");
   TORCH_CHECK(mse.size(0) == C && mse.size(1) == G);
   auto stream = at::cuda::getCurrentHIPStream();
-  auto fp = [](torch::Tensor& t) -> const float* {
-    return t.numel() ? t.data_ptr<float>() : nullptr;
-  };
   launch_groupfit_eval(
       yT.data_ptr<float>(), xc0.data_ptr<float>(), xc1.data_ptr<float>(),
       xc2.data_ptr<float>(), pj0.data_ptr<float>(), pj1.data_ptr<float>(),
       pj2.data_ptr<float>(), orders.data_ptr<int>(), mse.data_ptr<float>(),
       status.data_ptr<uint8_t>(),
-      fp(b0), fp(b1), fp(b2), fp(w0), fp(w1), fp(w2),
+      _f32_or_null(b0), _f32_or_null(b1), _f32_or_null(b2),
+      _f32_or_null(w0), _f32_or_null(w1), _f32_or_null(w2),
       T, G, (int)S, C, (int)xc0.size(1),
       stream.stream());
 }
@@ -133,16 +143,14 @@ void groupfit_final(torch::Tensor yT, torch::Tensor xc0, torch::Tensor xc1,
   long long G = yT.size(1);
   TORCH_CHECK(fitted.size(0) == T && fitted.size(1) == G);
   auto stream = at::cuda::getCurrentHIPStream();
-  auto fp = [](torch::Tensor& t) -> const float* {
-    return t.numel() ? t.data_ptr<float>() : nullptr;
-  };
   launch_groupfit_final(
       yT.data_ptr<float>(), xc0.data_ptr<float>(), xc1.data_ptr<float>(),
       xc2.data_ptr<float>(), pj0.data_ptr<float>(), pj1.data_ptr<float>(),
       pj2.data_ptr<float>(), best_order.data_ptr<int>(),
       fitted.data_ptr<float>(), params.data_ptr<float>(),
       status.data_ptr<uint8_t>(),
-      fp(b0), fp(b1), fp(b2), fp(w0), fp(w1), fp(w2),
+      _f32_or_null(b0), _f32_or_null(b1), _f32_or_null(b2),
+      _f32_or_null(w0), _f32_or_null(w1), _f32_or_null(w2),
       T, G, (int)xc0.size(1), stream.stream());
 }
 
@@ -294,18 +302,12 @@ extern "C" void launch_bn_fwd_apply(const void* x, const void* res, void* y,
                                     const float* weight, const float* bias,
                                     long long rows, int C, int relu,
                                     hipStream_t stream);
-extern "C" void launch_bn_bwd_reduce(const void* dz, const void* y,
-                                     const void* x, const float* mean,
-                                     const float* invstd, float* partial,
-                                     void* dym, int nblocks, long long rows,
-                                     int C, int relu, hipStream_t stream);
-extern "C" void launch_bn_bwd_reduce_join(const void* dz1, const void* dz2,
-                                          const void* y, const void* x,
-                                          const float* mean,
-                                          const float* invstd,
-                                          float* partial, void* dym,
-                                          int nblocks, long long rows, int C,
-                                          int relu, hipStream_t stream);
+extern "C" void launch_bn_bwd_reduce(const void* dz, const void* dz2,
+                                     const void* y, const void* x,
+                                     const float* mean, const float* invstd,
+                                     float* partial, void* dym, int nblocks,
+                                     long long rows, int C, int relu,
+                                     hipStream_t stream);
 extern "C" void launch_bn_bwd_reduce_rm(const void* dz, const void* x,
                                         const float* mean,
                                         const float* invstd,
@@ -344,20 +346,41 @@ static void _check_bn_act(const torch::Tensor& t, const char* name) {
               name, " must be bf16 on GPU");
 }
 
-static long long _bn_rows(const torch::Tensor& x, int64_t C) {
+// One 256-thread block must tile whole rows of C/8 vector lanes.
+static void _check_bn_channels(int64_t C) {
   TORCH_CHECK(C % 8 == 0 && 256 % (C / 8) == 0,
               "C must be 8*2^k and <= 2048, got ", C);
+}
+
+static long long _bn_rows(const torch::Tensor& x, int64_t C) {
+  _check_bn_channels(C);
   TORCH_CHECK(x.numel() % C == 0, "numel not divisible by C");
   return (long long)(x.numel() / C);
+}
+
+// Optional activation map: an undefined or empty tensor means "not given"
+// and yields a null pointer; a given one must be bf16 on the GPU with as
+// many elements as the map it goes with.
+static void* _opt_bn_act(const torch::Tensor& t, const char* name,
+                         int64_t numel) {
+  if (!t.defined() || !t.numel()) return nullptr;
+  _check_bn_act(t, name);
+  TORCH_CHECK(t.numel() == numel, name, " shape mismatch");
+  return t.data_ptr();
+}
+
+// The reduce kernels' fp32 partial, [2C][nb] with nb the block count.
+static torch::Tensor _bn_partial(const torch::Tensor& x, int nb, int64_t C) {
+  return torch::empty(
+      {(int64_t)nb * 2 * C},
+      torch::TensorOptions().dtype(torch::kFloat32).device(x.device()));
 }
 
 torch::Tensor bn_fwd_reduce(torch::Tensor x, int64_t C) {
   _check_bn_act(x, "x");
   long long rows = _bn_rows(x, C);
   int nb = bn_reduce_blocks(rows, (int)C);
-  auto partial = torch::empty(
-      {(int64_t)nb * 2 * C},
-      torch::TensorOptions().dtype(torch::kFloat32).device(x.device()));
+  auto partial = _bn_partial(x, nb, C);
   launch_bn_fwd_reduce(x.data_ptr(), partial.data_ptr<float>(), nb, rows,
                        (int)C, at::cuda::getCurrentHIPStream().stream());
   return partial;
@@ -399,13 +422,8 @@ void bn_fwd_apply(torch::Tensor x, torch::Tensor res, torch::Tensor y,
   _check_bn_act(x, "x"); _check_bn_act(y, "y");
   _check_f32(mean, "mean"); _check_f32(invstd, "invstd");
   _check_f32(weight, "weight"); _check_f32(bias, "bias");
-  const void* res_p = nullptr;
-  if (res.defined() && res.numel()) {
-    _check_bn_act(res, "res");
-    TORCH_CHECK(res.numel() == x.numel(), "residual shape mismatch");
-    res_p = res.data_ptr();
-  }
-  launch_bn_fwd_apply(x.data_ptr(), res_p, y.data_ptr(),
+  launch_bn_fwd_apply(x.data_ptr(), _opt_bn_act(res, "res", x.numel()),
+                      y.data_ptr(),
                       mean.data_ptr<float>(), invstd.data_ptr<float>(),
                       weight.data_ptr<float>(), bias.data_ptr<float>(),
                       _bn_rows(x, C), (int)C, relu ? 1 : 0,
@@ -420,18 +438,11 @@ torch::Tensor bn_bwd_reduce(torch::Tensor dz, torch::Tensor y,
                             torch::Tensor invstd, torch::Tensor dym,
                             int64_t C, bool relu) {
   _check_bn_act(dz, "dz"); _check_bn_act(y, "y"); _check_bn_act(x, "x");
-  void* dym_p = nullptr;
-  if (dym.defined() && dym.numel()) {
-    _check_bn_act(dym, "dym");
-    TORCH_CHECK(dym.numel() == x.numel(), "dym shape mismatch");
-    dym_p = dym.data_ptr();
-  }
+  void* dym_p = _opt_bn_act(dym, "dym", x.numel());
   long long rows = _bn_rows(x, C);
   int nb = bn_reduce_blocks(rows, (int)C);
-  auto partial = torch::empty(
-      {(int64_t)nb * 2 * C},
-      torch::TensorOptions().dtype(torch::kFloat32).device(x.device()));
-  launch_bn_bwd_reduce(dz.data_ptr(), y.data_ptr(), x.data_ptr(),
+  auto partial = _bn_partial(x, nb, C);
+  launch_bn_bwd_reduce(dz.data_ptr(), nullptr, y.data_ptr(), x.data_ptr(),
                        mean.data_ptr<float>(), invstd.data_ptr<float>(),
                        partial.data_ptr<float>(), dym_p, nb, rows, (int)C,
                        relu ? 1 : 0,
@@ -464,15 +475,12 @@ torch::Tensor bn_bwd_reduce_join(torch::Tensor dz1, torch::Tensor dz2,
                 names[i], " must match x (channels_last)");
   long long rows = _bn_rows(x, C);
   int nb = bn_reduce_blocks(rows, (int)C);
-  auto partial = torch::empty(
-      {(int64_t)nb * 2 * C},
-      torch::TensorOptions().dtype(torch::kFloat32).device(x.device()));
-  launch_bn_bwd_reduce_join(dz1.data_ptr(), dz2.data_ptr(), y.data_ptr(),
-                            x.data_ptr(), mean.data_ptr<float>(),
-                            invstd.data_ptr<float>(),
-                            partial.data_ptr<float>(), dym.data_ptr(), nb,
-                            rows, (int)C, relu ? 1 : 0,
-                            at::cuda::getCurrentHIPStream().stream());
+  auto partial = _bn_partial(x, nb, C);
+  launch_bn_bwd_reduce(dz1.data_ptr(), dz2.data_ptr(), y.data_ptr(),
+                       x.data_ptr(), mean.data_ptr<float>(),
+                       invstd.data_ptr<float>(), partial.data_ptr<float>(),
+                       dym.data_ptr(), nb, rows, (int)C, relu ? 1 : 0,
+                       at::cuda::getCurrentHIPStream().stream());
   return partial;
 }
 
@@ -485,17 +493,10 @@ torch::Tensor bn_bwd_reduce_rm(torch::Tensor dz, torch::Tensor x,
   _check_bn_act(dz, "dz"); _check_bn_act(x, "x");
   _check_f32(mean, "mean"); _check_f32(invstd, "invstd");
   _check_f32(weight, "weight"); _check_f32(bias, "bias");
-  void* dym_p = nullptr;
-  if (dym.defined() && dym.numel()) {
-    _check_bn_act(dym, "dym");
-    TORCH_CHECK(dym.numel() == x.numel(), "dym shape mismatch");
-    dym_p = dym.data_ptr();
-  }
+  void* dym_p = _opt_bn_act(dym, "dym", x.numel());
   long long rows = _bn_rows(x, C);
   int nb = bn_reduce_blocks(rows, (int)C);
-  auto partial = torch::empty(
-      {(int64_t)nb * 2 * C},
-      torch::TensorOptions().dtype(torch::kFloat32).device(x.device()));
+  auto partial = _bn_partial(x, nb, C);
   launch_bn_bwd_reduce_rm(dz.data_ptr(), x.data_ptr(),
                           mean.data_ptr<float>(), invstd.data_ptr<float>(),
                           weight.data_ptr<float>(), bias.data_ptr<float>(),
@@ -556,11 +557,7 @@ void bn_bwd_apply(torch::Tensor dz, torch::Tensor y, torch::Tensor x,
   _check_bn_act(dx, "dx");
   _check_f32(mean, "mean"); _check_f32(invstd, "invstd");
   _check_f32(k, "k");
-  void* dres_p = nullptr;
-  if (dres.defined() && dres.numel()) {
-    _check_bn_act(dres, "dres");
-    dres_p = dres.data_ptr();
-  }
+  void* dres_p = _opt_bn_act(dres, "dres", x.numel());
   launch_bn_bwd_apply(dz.data_ptr(), y.data_ptr(), x.data_ptr(),
                       mean.data_ptr<float>(), invstd.data_ptr<float>(),
                       k.data_ptr<float>(), dx.data_ptr(), dres_p,
@@ -616,10 +613,10 @@ extern "C" void launch_maxpool_bwd(const void* dy,
 void maxpool3x3s2_fwd(torch::Tensor x, torch::Tensor y,
                       torch::Tensor code) {
   _check_bn_act(x, "x"); _check_bn_act(y, "y");
-  TORCH_CHECK(code.scalar_type() == torch::kUInt8 && code.is_cuda());
+  _check_code(code);
   int N = x.size(0), C = x.size(1), H = x.size(2), W = x.size(3);
   int Ho = y.size(2), Wo = y.size(3);
-  TORCH_CHECK(C % 8 == 0 && 256 % (C / 8) == 0, "bad C");
+  _check_bn_channels(C);
   TORCH_CHECK(Ho == (H + 1) / 2 && Wo == (W + 1) / 2, "3x3 s2 p1 shape");
   TORCH_CHECK(code.numel() == y.numel());
   launch_maxpool_fwd(x.data_ptr(), y.data_ptr(), code.data_ptr<uint8_t>(),
@@ -636,10 +633,10 @@ void bn_maxpool3x3s2_fwd(torch::Tensor x, torch::Tensor mean,
   _check_bn_act(x, "x"); _check_bn_act(y, "y");
   _check_f32(mean, "mean"); _check_f32(invstd, "invstd");
   _check_f32(weight, "weight"); _check_f32(bias, "bias");
-  TORCH_CHECK(code.scalar_type() == torch::kUInt8 && code.is_cuda());
+  _check_code(code);
   int N = x.size(0), C = x.size(1), H = x.size(2), W = x.size(3);
   int Ho = y.size(2), Wo = y.size(3);
-  TORCH_CHECK(C % 8 == 0 && 256 % (C / 8) == 0, "bad C");
+  _check_bn_channels(C);
   TORCH_CHECK(Ho == (H + 1) / 2 && Wo == (W + 1) / 2, "3x3 s2 p1 shape");
   TORCH_CHECK(code.numel() == y.numel());
   launch_bn_maxpool_fwd(x.data_ptr(), mean.data_ptr<float>(),
@@ -653,7 +650,7 @@ void bn_maxpool3x3s2_fwd(torch::Tensor x, torch::Tensor mean,
 void maxpool3x3s2_bwd(torch::Tensor dy, torch::Tensor code,
                       torch::Tensor dx) {
   _check_bn_act(dy, "dy"); _check_bn_act(dx, "dx");
-  TORCH_CHECK(code.scalar_type() == torch::kUInt8 && code.is_cuda());
+  _check_code(code);
   int N = dx.size(0), C = dx.size(1), H = dx.size(2), W = dx.size(3);
   int Ho = dy.size(2), Wo = dy.size(3);
   TORCH_CHECK(code.numel() == dy.numel());
@@ -673,16 +670,14 @@ static _PoolGeom _check_bn_pool_bwd(const torch::Tensor& dp,
                                     const torch::Tensor& code,
                                     const torch::Tensor& x) {
   _check_bn_act(dp, "dp"); _check_bn_act(x, "x");
-  TORCH_CHECK(code.scalar_type() == torch::kUInt8 && code.is_cuda() &&
-                  code.is_contiguous(),
-              "code must be contiguous u8 on GPU");
+  _check_code(code);
   TORCH_CHECK(x.dim() == 4 && dp.dim() == 4, "x and dp must be 4-d");
   TORCH_CHECK(x.is_contiguous(at::MemoryFormat::ChannelsLast) &&
                   dp.is_contiguous(at::MemoryFormat::ChannelsLast),
               "x and dp must be channels_last");
   _PoolGeom g{(int)x.size(0), (int)x.size(1), (int)x.size(2),
               (int)x.size(3), (int)dp.size(2), (int)dp.size(3)};
-  TORCH_CHECK(g.C % 8 == 0 && 256 % (g.C / 8) == 0, "bad C");
+  _check_bn_channels(g.C);
   TORCH_CHECK(dp.size(0) == g.N && dp.size(1) == g.C, "dp N/C mismatch");
   TORCH_CHECK(g.Ho == (g.H + 1) / 2 && g.Wo == (g.W + 1) / 2,
               "3x3 s2 p1 shape");
@@ -704,9 +699,7 @@ torch::Tensor bn_pool_bwd_reduce(torch::Tensor dp, torch::Tensor code,
                   weight.numel() == g.C && bias.numel() == g.C,
               "channel vectors must be [C]");
   int nb = bn_reduce_blocks((long long)g.N * g.Ho * g.Wo, g.C);
-  auto partial = torch::empty(
-      {(int64_t)nb * 2 * g.C},
-      torch::TensorOptions().dtype(torch::kFloat32).device(x.device()));
+  auto partial = _bn_partial(x, nb, g.C);
   launch_bn_pool_bwd_reduce(dp.data_ptr(), code.data_ptr<uint8_t>(),
                             x.data_ptr(), mean.data_ptr<float>(),
                             invstd.data_ptr<float>(),
@@ -790,8 +783,8 @@ void adam_step_mixed(torch::Tensor master, torch::Tensor gb,
   long long nb = gb.numel();
   TORCH_CHECK(pb.numel() == nb && gf.numel() == n - nb &&
               m.numel() == n && v.numel() == n, "buffer length mismatch");
-  const float* gf_p = gf.numel() ? gf.data_ptr<float>() : nullptr;
-  launch_adam_step_mixed(master.data_ptr<float>(), gb.data_ptr(), gf_p,
+  launch_adam_step_mixed(master.data_ptr<float>(), gb.data_ptr(),
+                         _f32_or_null(gf),
                          m.data_ptr<float>(), v.data_ptr<float>(),
                          pb.data_ptr(), step.data_ptr<int>(), (float)lr,
                          (float)beta1, (float)beta2, (float)eps,
@@ -808,35 +801,46 @@ int64_t stem_fwd_blocks(int64_t Nb, int64_t HO) {
   return stem_fwd_stat_blocks((int)Nb, (int)HO);
 }
 
+// Geometry both stem entry points share: x [N,H,W,3] and the 64-channel
+// output-side map (out, or its gradient dy) [N,HO,WO,64], both bf16 on the
+// GPU and dense NHWC, related by 7x7 s2 p3.
+struct _StemGeom { int Nb, H, W, HO, WO; };
+
+static _StemGeom _check_stem_geom(const torch::Tensor& x,
+                                  const torch::Tensor& o) {
+  TORCH_CHECK(x.is_cuda() && x.scalar_type() == torch::kBFloat16);
+  TORCH_CHECK(o.is_cuda() && o.scalar_type() == torch::kBFloat16);
+  _StemGeom g{(int)x.size(0), (int)x.size(1), (int)x.size(2),
+              (int)o.size(1), (int)o.size(2)};
+  TORCH_CHECK(x.size(3) == 3 && o.size(3) == 64, "stem is 3->64");
+  TORCH_CHECK(g.WO <= 128, "stem kernel handles output rows up to 128 px");
+  TORCH_CHECK(x.is_contiguous() && o.is_contiguous() &&
+                  o.size(0) == g.Nb && g.HO == (g.H - 1) / 2 + 1 &&
+                  g.WO == (g.W - 1) / 2 + 1,
+              "stem conv: dense NHWC x and out/dy with 7x7 s2 p3 geometry");
+  return g;
+}
+
 void stem_conv_fwd(torch::Tensor x, torch::Tensor w, torch::Tensor out,
                    torch::Tensor wp_scratch, int64_t phase_mask = 7,
                    c10::optional<torch::Tensor> partial = c10::nullopt) {
-  TORCH_CHECK(x.is_cuda() && x.scalar_type() == torch::kBFloat16);
+  const _StemGeom g = _check_stem_geom(x, out);
   TORCH_CHECK(w.is_cuda() && w.scalar_type() == torch::kBFloat16);
-  TORCH_CHECK(out.is_cuda() && out.scalar_type() == torch::kBFloat16);
-  int Nb = x.size(0), H = x.size(1), W = x.size(2);
-  TORCH_CHECK(x.size(3) == 3 && out.size(3) == 64, "stem is 3->64");
-  int HO = out.size(1), WO = out.size(2);
-  TORCH_CHECK(WO <= 128, "stem kernel handles output rows up to 128 px");
   TORCH_CHECK(w.numel() == 64 * 7 * 7 * 3);
   TORCH_CHECK(wp_scratch.scalar_type() == torch::kBFloat16 &&
               wp_scratch.numel() == 64 * 160);
-  TORCH_CHECK(x.is_contiguous() && out.is_contiguous() &&
-                  out.size(0) == Nb && HO == (H - 1) / 2 + 1 &&
-                  WO == (W - 1) / 2 + 1,
-              "stem conv: dense NHWC x/out with 7x7 s2 p3 geometry");
   float* partial_p = nullptr;
   if (partial.has_value()) {
     const torch::Tensor& p = *partial;
     TORCH_CHECK(p.is_cuda() && p.scalar_type() == torch::kFloat32 &&
                     p.is_contiguous() &&
-                    p.numel() == 2 * 64 * stem_fwd_blocks(Nb, HO),
+                    p.numel() == 2 * 64 * stem_fwd_blocks(g.Nb, g.HO),
                 "partial must be fp32 [2*64*stem_fwd_blocks(N, HO)]");
     partial_p = p.data_ptr<float>();
   }
   launch_stem_conv_fwd(x.data_ptr(), w.data_ptr(), out.data_ptr(),
                        wp_scratch.data_ptr(), partial_p,
-                       Nb, H, W, HO, WO,
+                       g.Nb, g.H, g.W, g.HO, g.WO,
                        at::cuda::getCurrentHIPStream().stream(),
                        (int)phase_mask);
 }
@@ -850,29 +854,20 @@ int64_t stem_wrw_scratch() { return stem_wrw_scratch_elems(); }
 void stem_conv_wrw(torch::Tensor x, torch::Tensor dy, torch::Tensor dw_f32,
                    torch::Tensor dw, int64_t phase_mask = 7,
                    int64_t tr = -1) {
-  TORCH_CHECK(x.is_cuda() && x.scalar_type() == torch::kBFloat16);
-  TORCH_CHECK(dy.is_cuda() && dy.scalar_type() == torch::kBFloat16);
+  const _StemGeom g = _check_stem_geom(x, dy);
   TORCH_CHECK(dw_f32.is_cuda() && dw_f32.scalar_type() == torch::kFloat32 &&
                   dw_f32.is_contiguous() &&
                   dw_f32.numel() == stem_wrw_scratch(),
               "dw_f32 must be fp32 [stem_wrw_scratch()]");
   TORCH_CHECK(dw.scalar_type() == torch::kBFloat16 &&
               dw.numel() == 64 * 7 * 7 * 3);
-  int Nb = x.size(0), H = x.size(1), W = x.size(2);
-  int HO = dy.size(1), WO = dy.size(2);
-  TORCH_CHECK(x.size(3) == 3 && dy.size(3) == 64, "stem is 3->64");
-  TORCH_CHECK(WO <= 128, "stem kernel handles output rows up to 128 px");
-  TORCH_CHECK(x.is_contiguous() && dy.is_contiguous() &&
-                  dy.size(0) == Nb && HO == (H - 1) / 2 + 1 &&
-                  WO == (W - 1) / 2 + 1,
-              "stem conv: dense NHWC x/dy with 7x7 s2 p3 geometry");
   if (tr < 0) {
     const char* e = std::getenv("MI355X_STEM_WRW_TR");
     tr = !(e && e[0] == '0' && e[1] == 0);
   }
   launch_stem_conv_wrw(x.data_ptr(), dy.data_ptr(),
                        dw_f32.data_ptr<float>(), dw.data_ptr(),
-                       Nb, H, W, HO, WO,
+                       g.Nb, g.H, g.W, g.HO, g.WO,
                        at::cuda::getCurrentHIPStream().stream(),
                        (int)phase_mask, tr ? 1 : 0);
 }

@@ -8,38 +8,43 @@
 // with the adjacent ReLU and residual-add as further standalone
 // elementwise passes — together ~32% of step kernel time.
 //
-// This file fuses the whole thing at bf16 activation width:
-//   fwd:  reduce(x) -> finalize(mean/invstd + running stats) ->
-//         apply: y = [relu](bn(x) [+ residual])            (bf16 in/out)
-//   bwd:  reduce(dz,y,x) -> finalize -> apply: dx, dres    (bf16 in/out)
-// with fp32 accumulation throughout. The ReLU mask is recovered from the
-// saved output y (y > 0), so ReLU backward costs nothing; the residual
-// branch's gradient is the masked upstream gradient and is written by the
-// same backward pass.
+// This file fuses the whole thing at bf16 activation width, with fp32
+// accumulation throughout. Each direction is three stream-ordered passes:
+//   fwd:  reduce(x) -> finalize -> apply: y = [relu](bn(x) [+ residual])
+//   bwd:  reduce(dz, x, mask) -> finalize -> apply: dx [, dres]
+//   * reduce: every block sums its rows and writes one slot of a
+//     channel-major [2C][nblocks] fp32 partial (block_reduce_store, the
+//     one epilogue all five reduce kernels end in). No global atomics:
+//     the order of every sum is fixed, so graph replays are bit-stable.
+//   * finalize: one wavefront (or block, for long runs) per channel sums
+//     the slots. Forward writes mean/invstd, updates the running stats
+//     and bumps num_batches_tracked; backward writes dweight/dbias and
+//     the three per-channel constants k the apply pass needs.
+//   * apply: one streaming pass, one fma-sized expression per element.
+// The backward reduce comes in three forms, by where the relu mask and
+// the upstream gradient come from:
+//   * bn_bwd_reduce: mask from the saved output (y > 0). It can also
+//     store the masked gradient dym, which for a residual layer IS the
+//     residual branch's gradient and is all the apply pass then reads;
+//     and it can sum the gradients of an output's two consumers while it
+//     streams (JOIN), so autograd's stand-alone add does not run;
+//   * bn_bwd_*_rm (non-residual relu layers): mask recomputed as
+//     (w*xhat + b) > 0 from the x already in registers; y is not read;
+//   * bn_pool_bwd_* (stem): the same recompute-mask math in the tile
+//     order of the 3x3/s2 max-pool, with the un-pooled gradient rebuilt
+//     in registers from the pooled gradient and the u8 window codes.
 //
 // Layout/mapping (CDNA4-first):
 //   * activations are NHWC ("channels_last"), rows = N*H*W, C channels
 //     contiguous; every load/store is an 8-wide bf16 vector (16 B,
 //     dwordx4) so wavefronts of 64 lanes touch 1 KB per instruction.
 //   * a block of 256 threads (4 wavefronts) covers 256/(C/8) rows per
-//     iteration; grid-stride over rows; grids are sized >> 256 workgroups
-//     where the row count allows, to fill all 8 XCDs.
-//   * block-level partials are tree-reduced through LDS (16 KB of the
-//     160 KB/CU) and committed with fp32 global atomics (C <= 512 means
-//     contention is negligible).
+//     iteration (RowMap); grid-stride over rows; grids are sized >> 256
+//     workgroups where the row count allows, to fill all 8 XCDs.
+//   * block-level sums are tree-reduced through LDS (16 KB of the
+//     160 KB/CU) before the block's partial slot is written.
 // All kernels are stream-ordered device work with no host sync, so
 // the whole fused op captures into hipGraphs (train/graphstep.py).
-//
-// Later additions, described at their definitions below:
-//   * recompute-mask backward (bn_bwd_*_rm): the relu mask comes from
-//     (w*xhat + b) > 0, so the stored y is not read;
-//   * stem backward (bn_pool_bwd_*): the max-unpool of the pooled
-//     gradient is rebuilt in registers inside both passes, so the
-//     un-pooled map is never written or read;
-//   * bn_fwd_finalize also bumps the module's num_batches_tracked;
-//   * joined residual backward (bn_bwd_reduce_join): a block output has
-//     two consumers, and the reduce reads their two gradients itself, so
-//     autograd's stand-alone add of the two maps does not run.
 //
 // Reference parity: this implements the BatchNorm2d semantics the
 // reference's torchvision resnet50 relies on
@@ -68,26 +73,146 @@ static __device__ __forceinline__ void store8(bf16* p, const BVec& v) {
   *reinterpret_cast<uint4*>(p) = v.u;
 }
 
+// --------------------------------------------------------- shared skeleton
+// Thread decomposition of every streaming kernel: `lanes` threads cover
+// one row (8 channels each), so a 256-thread block advances
+// rows_per_iter rows at a time, grid-stride. The stem's tile-order
+// kernels walk 2x2 tiles instead of rows with the same mapping.
+//
+// Built in two steps, `RowMap t(C); t.span(blockDim.x);`: blockDim.x folds
+// to one scalar load only when the __global__ function itself reads it,
+// after the lane split (profiles/r07_fused_bn_refactor_isa.md).
+struct RowMap {
+  int C;
+  int lanes;          // vector-lanes per row
+  int lane;           // which 8-channel slot
+  int rsub;           // row within the block's tile
+  int rows_per_iter;
+  long long rstride;
+
+  __device__ __forceinline__ explicit RowMap(int C_)
+      : C(C_),
+        lanes(C_ / VEC),
+        lane(threadIdx.x % lanes),
+        rsub(threadIdx.x / lanes) {}
+
+  __device__ __forceinline__ void span(unsigned block_threads) {
+    rows_per_iter = block_threads / lanes;
+    rstride = (long long)gridDim.x * rows_per_iter;
+  }
+
+  // this thread's first row (or tile)
+  __device__ __forceinline__ long long first_row() const {
+    return (long long)blockIdx.x * rows_per_iter + rsub;
+  }
+
+  // element offset of this thread's 8 channels in `row`
+  __device__ __forceinline__ long long off(long long row) const {
+    return row * C + (long long)lane * VEC;
+  }
+};
+
+// Per-lane channel constants of the backward kernels: mean and invstd, and
+// in the second form weight and bias as well (the kernels that recompute
+// the relu mask). Loads are issued channel by channel, from per-lane base
+// pointers: indexing each vector with lane * VEC + j instead leaves eight
+// channel indices live across the kernel's main loop
+// (profiles/r07_fused_bn_refactor_isa.md).
+static __device__ __forceinline__ void load_stats(
+    const RowMap& t, const float* mean, const float* invstd,
+    float (&m)[VEC], float (&is)[VEC]) {
+  mean += t.lane * VEC;
+  invstd += t.lane * VEC;
+#pragma unroll
+  for (int j = 0; j < VEC; ++j) {
+    m[j] = mean[j];
+    is[j] = invstd[j];
+  }
+}
+
+static __device__ __forceinline__ void load_stats(
+    const RowMap& t, const float* mean, const float* invstd,
+    const float* weight, const float* bias, float (&m)[VEC],
+    float (&is)[VEC], float (&wv)[VEC], float (&bv)[VEC]) {
+  mean += t.lane * VEC;
+  invstd += t.lane * VEC;
+  weight += t.lane * VEC;
+  bias += t.lane * VEC;
+#pragma unroll
+  for (int j = 0; j < VEC; ++j) {
+    m[j] = mean[j];
+    is[j] = invstd[j];
+    wv[j] = weight[j];
+    bv[j] = bias[j];
+  }
+}
+
+// The apply kernels' constants from bn_bwd_finalize: k = [w*invstd,
+// mean_dy, mean_dy_xhat], C floats each.
+static __device__ __forceinline__ void load_k(
+    const RowMap& t, const float* k, float (&wis)[VEC], float (&k1)[VEC],
+    float (&k2)[VEC]) {
+#pragma unroll
+  for (int j = 0; j < VEC; ++j) {
+    int c = t.lane * VEC + j;
+    wis[j] = k[c];
+    k1[j] = k[t.C + c];
+    k2[j] = k[2 * t.C + c];
+  }
+}
+
+// Epilogue of every reduce kernel: tree-reduce the block's two per-thread
+// accumulators across the rows_per_iter threads sharing each lane, then
+// write the block's slot of the channel-major partial [2C][nblocks] (`a`
+// to channels [0, C), `b` to [C, 2C)): the finalize wavefront for channel
+// c then reads a contiguous nblocks-float run.
+//
+// Two-stage rather than global atomics — a single fp32 atomic target
+// serializes one RMW per block (measured 406 us/call at 2080 blocks on
+// MI355X, ~20x the memory-bound cost of the pass) and is
+// non-deterministic across graph replays.
+static __device__ __forceinline__ void block_reduce_store(
+    const RowMap& t, const float (&a)[VEC], const float (&b)[VEC],
+    float* partial) {
+  __shared__ float lds[256 * 2 * VEC];
+  float* mys = &lds[(t.rsub * t.lanes + t.lane) * 2 * VEC];
+#pragma unroll
+  for (int j = 0; j < VEC; ++j) {
+    mys[j] = a[j];
+    mys[VEC + j] = b[j];
+  }
+  __syncthreads();
+  for (int step = t.rows_per_iter >> 1; step > 0; step >>= 1) {
+    if (t.rsub < step) {
+      const float* other =
+          &lds[((t.rsub + step) * t.lanes + t.lane) * 2 * VEC];
+#pragma unroll
+      for (int j = 0; j < 2 * VEC; ++j) mys[j] += other[j];
+    }
+    __syncthreads();
+  }
+  if (t.rsub == 0) {
+#pragma unroll
+    for (int j = 0; j < VEC; ++j) {
+      partial[(long long)(t.lane * VEC + j) * gridDim.x + blockIdx.x] =
+          mys[j];
+      partial[(long long)(t.C + t.lane * VEC + j) * gridDim.x +
+              blockIdx.x] = mys[VEC + j];
+    }
+  }
+}
+
 // ---------------------------------------------------------------- fwd reduce
-// Two-stage reduction: every block writes its own [2C] partial slot
-// (partial[block*2C + c] = block-sum x_c, [.. + C + c] = block-sum x_c^2);
-// the finalize kernel sums across blocks. No global atomics — a single
-// fp32 atomic target serializes one RMW per block (measured 406 us/call
-// at 2080 blocks on MI355X, ~20x the memory-bound cost of the pass) and
-// is non-deterministic across graph replays.
+// partial[c][block] = block-sum x_c, partial[C + c][block] = block-sum
+// x_c^2; the finalize kernel sums across blocks.
 __global__ __launch_bounds__(256) void bn_fwd_reduce_kernel(
     const bf16* __restrict__ x, float* __restrict__ partial,
     long long rows, int C) {
-  const int lanes = C / VEC;            // vector-lanes per row
-  const int lane = threadIdx.x % lanes; // which 8-channel slot
-  const int rsub = threadIdx.x / lanes; // row within the block's tile
-  const int rows_per_iter = blockDim.x / lanes;
-  const long long rstride = (long long)gridDim.x * rows_per_iter;
-
+  RowMap t(C);
+  t.span(blockDim.x);
   float s[VEC] = {0.f}, q[VEC] = {0.f};
-  for (long long row = (long long)blockIdx.x * rows_per_iter + rsub;
-       row < rows; row += rstride) {
-    BVec v = load8(x + row * C + (long long)lane * VEC);
+  for (long long row = t.first_row(); row < rows; row += t.rstride) {
+    BVec v = load8(x + t.off(row));
 #pragma unroll
     for (int j = 0; j < VEC; ++j) {
       float f = __bfloat162float(v.h[j]);
@@ -95,34 +220,7 @@ __global__ __launch_bounds__(256) void bn_fwd_reduce_kernel(
       q[j] += f * f;
     }
   }
-
-  // Tree-reduce across the rows_per_iter threads sharing each lane.
-  __shared__ float lds[256 * 2 * VEC];
-  float* mys = &lds[(rsub * lanes + lane) * 2 * VEC];
-#pragma unroll
-  for (int j = 0; j < VEC; ++j) {
-    mys[j] = s[j];
-    mys[VEC + j] = q[j];
-  }
-  __syncthreads();
-  for (int step = rows_per_iter >> 1; step > 0; step >>= 1) {
-    if (rsub < step) {
-      const float* other = &lds[((rsub + step) * lanes + lane) * 2 * VEC];
-#pragma unroll
-      for (int j = 0; j < 2 * VEC; ++j) mys[j] += other[j];
-    }
-    __syncthreads();
-  }
-  if (rsub == 0) {
-    // channel-major partial layout [2C][nblocks]: the finalize wavefront
-    // for channel c then reads a contiguous nblocks-float run.
-#pragma unroll
-    for (int j = 0; j < VEC; ++j) {
-      partial[(long long)(lane * VEC + j) * gridDim.x + blockIdx.x] = mys[j];
-      partial[(long long)(C + lane * VEC + j) * gridDim.x + blockIdx.x] =
-          mys[VEC + j];
-    }
-  }
+  block_reduce_store(t, s, q, partial);
 }
 
 // -------------------------------------------------------------- fwd finalize
@@ -241,23 +339,18 @@ __global__ __launch_bounds__(256) void bn_fwd_apply_kernel(
     bf16* __restrict__ y, const float* __restrict__ mean,
     const float* __restrict__ invstd, const float* __restrict__ weight,
     const float* __restrict__ bias, long long rows, int C) {
-  const int lanes = C / VEC;
-  const int lane = threadIdx.x % lanes;
-  const int rsub = threadIdx.x / lanes;
-  const int rows_per_iter = blockDim.x / lanes;
-  const long long rstride = (long long)gridDim.x * rows_per_iter;
-
+  RowMap t(C);
+  t.span(blockDim.x);
   float a[VEC], b[VEC];
 #pragma unroll
   for (int j = 0; j < VEC; ++j) {
-    int c = lane * VEC + j;
+    int c = t.lane * VEC + j;
     a[j] = weight[c] * invstd[c];
     b[j] = bias[c] - mean[c] * a[j];
   }
 
-  for (long long row = (long long)blockIdx.x * rows_per_iter + rsub;
-       row < rows; row += rstride) {
-    const long long off = row * C + (long long)lane * VEC;
+  for (long long row = t.first_row(); row < rows; row += t.rstride) {
+    const long long off = t.off(row);
     BVec v = load8(x + off);
     BVec r;
     if (RES) r = load8(res + off);
@@ -274,36 +367,40 @@ __global__ __launch_bounds__(256) void bn_fwd_apply_kernel(
 }
 
 // ---------------------------------------------------------------- bwd reduce
-// dy = relu-masked upstream grad (mask = saved y > 0). Per-block partial
-// slots (same two-stage scheme as the forward). When WRITE_DY, the
-// masked dy is also materialized to dym: for residual layers dym IS the
-// residual-branch gradient, and the apply pass then reads (dym, x)
-// instead of (dz, y, x) — one read and one write less per layer.
-template <bool RELU, bool WRITE_DY>
+// dy = relu-masked upstream grad (mask = saved y > 0); partial holds the
+// block sums of dy and dy*xhat. When WRITE_DY, the masked dy is also
+// materialized to dym: for residual layers dym IS the residual-branch
+// gradient, and the apply pass then reads (dym, x) instead of (dz, y, x)
+// — one read and one write less per layer.
+//
+// JOIN is the residual-layer reduce for an output with TWO consumers (the
+// next block's conv1 and its identity path / downsample conv). Autograd
+// would sum the two incoming gradients with a stand-alone elementwise add
+// (2 maps read, 1 written) right in front of this kernel, which reads
+// that sum exactly once. Here the kernel reads both addends itself: one
+// extra map read, no add kernel. Per element dy = bf16(float(dz) +
+// float(dz2)), widened again — exactly the value the bf16 add kernel
+// stored — so mask, sdy, sdyx and dym are bit-identical to the one-gradient
+// kernel run on the summed map. All four 16 B loads of a row are issued
+// before the first use.
+template <bool RELU, bool WRITE_DY, bool JOIN>
 __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(
-    const bf16* __restrict__ dz, const bf16* __restrict__ y,
-    const bf16* __restrict__ x, const float* __restrict__ mean,
-    const float* __restrict__ invstd, float* __restrict__ partial,
-    bf16* __restrict__ dym, long long rows, int C) {
-  const int lanes = C / VEC;
-  const int lane = threadIdx.x % lanes;
-  const int rsub = threadIdx.x / lanes;
-  const int rows_per_iter = blockDim.x / lanes;
-  const long long rstride = (long long)gridDim.x * rows_per_iter;
-
+    const bf16* __restrict__ dz, const bf16* __restrict__ dz2,
+    const bf16* __restrict__ y, const bf16* __restrict__ x,
+    const float* __restrict__ mean, const float* __restrict__ invstd,
+    float* __restrict__ partial, bf16* __restrict__ dym, long long rows,
+    int C) {
+  RowMap t(C);
+  t.span(blockDim.x);
   float m[VEC], is[VEC];
-#pragma unroll
-  for (int j = 0; j < VEC; ++j) {
-    int c = lane * VEC + j;
-    m[j] = mean[c];
-    is[j] = invstd[c];
-  }
+  load_stats(t, mean, invstd, m, is);
 
   float sdy[VEC] = {0.f}, sdyx[VEC] = {0.f};
-  for (long long row = (long long)blockIdx.x * rows_per_iter + rsub;
-       row < rows; row += rstride) {
-    const long long off = row * C + (long long)lane * VEC;
+  for (long long row = t.first_row(); row < rows; row += t.rstride) {
+    const long long off = t.off(row);
     BVec g = load8(dz + off);
+    BVec g2;
+    if (JOIN) g2 = load8(dz2 + off);
     BVec xv = load8(x + off);
     BVec yv;
     if (RELU) yv = load8(y + off);
@@ -311,6 +408,10 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(
 #pragma unroll
     for (int j = 0; j < VEC; ++j) {
       float dy = __bfloat162float(g.h[j]);
+      // round the sum to bf16 first: that is what the add kernel stored
+      if (JOIN)
+        dy = __bfloat162float(
+            __float2bfloat16(dy + __bfloat162float(g2.h[j])));
       if (RELU && __bfloat162float(yv.h[j]) <= 0.f) dy = 0.f;
       float xhat = (__bfloat162float(xv.h[j]) - m[j]) * is[j];
       sdy[j] += dy;
@@ -319,117 +420,7 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(
     }
     if (WRITE_DY) store8(dym + off, dyv);
   }
-
-  __shared__ float lds[256 * 2 * VEC];
-  float* mys = &lds[(rsub * lanes + lane) * 2 * VEC];
-#pragma unroll
-  for (int j = 0; j < VEC; ++j) {
-    mys[j] = sdy[j];
-    mys[VEC + j] = sdyx[j];
-  }
-  __syncthreads();
-  for (int step = rows_per_iter >> 1; step > 0; step >>= 1) {
-    if (rsub < step) {
-      const float* other = &lds[((rsub + step) * lanes + lane) * 2 * VEC];
-#pragma unroll
-      for (int j = 0; j < 2 * VEC; ++j) mys[j] += other[j];
-    }
-    __syncthreads();
-  }
-  if (rsub == 0) {
-    // channel-major partial layout [2C][nblocks] (see forward reduce)
-#pragma unroll
-    for (int j = 0; j < VEC; ++j) {
-      partial[(long long)(lane * VEC + j) * gridDim.x + blockIdx.x] = mys[j];
-      partial[(long long)(C + lane * VEC + j) * gridDim.x + blockIdx.x] =
-          mys[VEC + j];
-    }
-  }
-}
-
-// ------------------------------------------------- bwd reduce, joined grads
-// Residual-layer reduce for an output with TWO consumers (the next block's
-// conv1 and its identity path / downsample conv). Autograd would sum the
-// two incoming gradients with a stand-alone elementwise add (2 maps read,
-// 1 written) right in front of this kernel, which reads that sum exactly
-// once. Here the kernel reads both addends itself: one extra map read, no
-// add kernel. Per element dy = bf16(float(dz1) + float(dz2)), widened
-// again — exactly the value the bf16 add kernel stored — so mask, sdy,
-// sdyx and dym are bit-identical to bn_bwd_reduce_kernel<RELU, true> run
-// on the summed map. A sibling kernel rather than a third template flag,
-// so the one-gradient instantiations stay what they are. Grid sizing,
-// LDS tree, partial layout and finalize are the one-gradient kernel's.
-// All four 16 B loads of a row are issued before the first use.
-template <bool RELU>
-__global__ __launch_bounds__(256) void bn_bwd_reduce_join_kernel(
-    const bf16* __restrict__ dz1, const bf16* __restrict__ dz2,
-    const bf16* __restrict__ y, const bf16* __restrict__ x,
-    const float* __restrict__ mean, const float* __restrict__ invstd,
-    float* __restrict__ partial, bf16* __restrict__ dym, long long rows,
-    int C) {
-  const int lanes = C / VEC;
-  const int lane = threadIdx.x % lanes;
-  const int rsub = threadIdx.x / lanes;
-  const int rows_per_iter = blockDim.x / lanes;
-  const long long rstride = (long long)gridDim.x * rows_per_iter;
-
-  float m[VEC], is[VEC];
-#pragma unroll
-  for (int j = 0; j < VEC; ++j) {
-    int c = lane * VEC + j;
-    m[j] = mean[c];
-    is[j] = invstd[c];
-  }
-
-  float sdy[VEC] = {0.f}, sdyx[VEC] = {0.f};
-  for (long long row = (long long)blockIdx.x * rows_per_iter + rsub;
-       row < rows; row += rstride) {
-    const long long off = row * C + (long long)lane * VEC;
-    BVec g1 = load8(dz1 + off);
-    BVec g2 = load8(dz2 + off);
-    BVec xv = load8(x + off);
-    BVec yv;
-    if (RELU) yv = load8(y + off);
-    BVec dyv;
-#pragma unroll
-    for (int j = 0; j < VEC; ++j) {
-      // round the sum to bf16 first: that is what the add kernel stored
-      float dy = __bfloat162float(__float2bfloat16(
-          __bfloat162float(g1.h[j]) + __bfloat162float(g2.h[j])));
-      if (RELU && __bfloat162float(yv.h[j]) <= 0.f) dy = 0.f;
-      float xhat = (__bfloat162float(xv.h[j]) - m[j]) * is[j];
-      sdy[j] += dy;
-      sdyx[j] += dy * xhat;
-      dyv.h[j] = __float2bfloat16(dy);
-    }
-    store8(dym + off, dyv);
-  }
-
-  __shared__ float lds[256 * 2 * VEC];
-  float* mys = &lds[(rsub * lanes + lane) * 2 * VEC];
-#pragma unroll
-  for (int j = 0; j < VEC; ++j) {
-    mys[j] = sdy[j];
-    mys[VEC + j] = sdyx[j];
-  }
-  __syncthreads();
-  for (int step = rows_per_iter >> 1; step > 0; step >>= 1) {
-    if (rsub < step) {
-      const float* other = &lds[((rsub + step) * lanes + lane) * 2 * VEC];
-#pragma unroll
-      for (int j = 0; j < 2 * VEC; ++j) mys[j] += other[j];
-    }
-    __syncthreads();
-  }
-  if (rsub == 0) {
-    // channel-major partial layout [2C][nblocks] (see forward reduce)
-#pragma unroll
-    for (int j = 0; j < VEC; ++j) {
-      partial[(long long)(lane * VEC + j) * gridDim.x + blockIdx.x] = mys[j];
-      partial[(long long)(C + lane * VEC + j) * gridDim.x + blockIdx.x] =
-          mys[VEC + j];
-    }
-  }
+  block_reduce_store(t, sdy, sdyx, partial);
 }
 
 // -------------------------------------------------------------- bwd finalize
@@ -464,76 +455,25 @@ __global__ __launch_bounds__(256) void bn_bwd_finalize_kernel(
   k[2 * C + c] = sdyx / (float)rows;
 }
 
-// ------------------------------------------------------- bwd apply (dym)
-// Residual-layer variant: reads the pre-masked dym written by the
-// reduce pass (which doubles as the residual gradient) + x; writes dx.
-__global__ __launch_bounds__(256) void bn_bwd_apply_dym_kernel(
-    const bf16* __restrict__ dym, const bf16* __restrict__ x,
-    const float* __restrict__ mean, const float* __restrict__ invstd,
-    const float* __restrict__ k, bf16* __restrict__ dx, long long rows,
-    int C) {
-  const int lanes = C / VEC;
-  const int lane = threadIdx.x % lanes;
-  const int rsub = threadIdx.x / lanes;
-  const int rows_per_iter = blockDim.x / lanes;
-  const long long rstride = (long long)gridDim.x * rows_per_iter;
-
-  float m[VEC], is[VEC], wv[VEC], k1[VEC], k2[VEC];
-#pragma unroll
-  for (int j = 0; j < VEC; ++j) {
-    int c = lane * VEC + j;
-    m[j] = mean[c];
-    is[j] = invstd[c];
-    wv[j] = k[c];
-    k1[j] = k[C + c];
-    k2[j] = k[2 * C + c];
-  }
-
-  for (long long row = (long long)blockIdx.x * rows_per_iter + rsub;
-       row < rows; row += rstride) {
-    const long long off = row * C + (long long)lane * VEC;
-    BVec g = load8(dym + off);
-    BVec xv = load8(x + off);
-    BVec odx;
-#pragma unroll
-    for (int j = 0; j < VEC; ++j) {
-      float dy = __bfloat162float(g.h[j]);
-      float xhat = (__bfloat162float(xv.h[j]) - m[j]) * is[j];
-      odx.h[j] = __float2bfloat16(wv[j] * (dy - k1[j] - xhat * k2[j]));
-    }
-    store8(dx + off, odx);
-  }
-}
-
 // ---------------------------------------------------------------- bwd apply
 // dx = w*invstd * (dy - mean_dy - xhat*mean_dy_xhat), with xhat
 // recomputed from (x-mean)*invstd and dy relu-masked; dres = dy.
+// <false, false> is also the residual layers' second pass: given the
+// pre-masked dym the reduce wrote as dz, it reads (dym, x) and never y.
 template <bool RELU, bool RES>
 __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(
     const bf16* __restrict__ dz, const bf16* __restrict__ y,
     const bf16* __restrict__ x, const float* __restrict__ mean,
     const float* __restrict__ invstd, const float* __restrict__ k,
     bf16* __restrict__ dx, bf16* __restrict__ dres, long long rows, int C) {
-  const int lanes = C / VEC;
-  const int lane = threadIdx.x % lanes;
-  const int rsub = threadIdx.x / lanes;
-  const int rows_per_iter = blockDim.x / lanes;
-  const long long rstride = (long long)gridDim.x * rows_per_iter;
+  RowMap t(C);
+  t.span(blockDim.x);
+  float m[VEC], is[VEC], wis[VEC], k1[VEC], k2[VEC];
+  load_stats(t, mean, invstd, m, is);
+  load_k(t, k, wis, k1, k2);
 
-  float m[VEC], is[VEC], wv[VEC], k1[VEC], k2[VEC];
-#pragma unroll
-  for (int j = 0; j < VEC; ++j) {
-    int c = lane * VEC + j;
-    m[j] = mean[c];
-    is[j] = invstd[c];
-    wv[j] = k[c];
-    k1[j] = k[C + c];
-    k2[j] = k[2 * C + c];
-  }
-
-  for (long long row = (long long)blockIdx.x * rows_per_iter + rsub;
-       row < rows; row += rstride) {
-    const long long off = row * C + (long long)lane * VEC;
+  for (long long row = t.first_row(); row < rows; row += t.rstride) {
+    const long long off = t.off(row);
     BVec g = load8(dz + off);
     BVec xv = load8(x + off);
     BVec yv;
@@ -544,7 +484,7 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(
       float dy = __bfloat162float(g.h[j]);
       if (RELU && __bfloat162float(yv.h[j]) <= 0.f) dy = 0.f;
       float xhat = (__bfloat162float(xv.h[j]) - m[j]) * is[j];
-      float v = wv[j] * (dy - k1[j] - xhat * k2[j]);
+      float v = wis[j] * (dy - k1[j] - xhat * k2[j]);
       odx.h[j] = __float2bfloat16(v);
       if (RES) odr.h[j] = __float2bfloat16(dy);
     }
@@ -593,26 +533,14 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_rm_kernel(
     const float* __restrict__ weight, const float* __restrict__ bias,
     float* __restrict__ partial, bf16* __restrict__ dym,
     long long rows, int C) {
-  const int lanes = C / VEC;
-  const int lane = threadIdx.x % lanes;
-  const int rsub = threadIdx.x / lanes;
-  const int rows_per_iter = blockDim.x / lanes;
-  const long long rstride = (long long)gridDim.x * rows_per_iter;
-
+  RowMap t(C);
+  t.span(blockDim.x);
   float m[VEC], is[VEC], wv[VEC], bv[VEC];
-#pragma unroll
-  for (int j = 0; j < VEC; ++j) {
-    int c = lane * VEC + j;
-    m[j] = mean[c];
-    is[j] = invstd[c];
-    wv[j] = weight[c];
-    bv[j] = bias[c];
-  }
+  load_stats(t, mean, invstd, weight, bias, m, is, wv, bv);
 
   float sdy[VEC] = {0.f}, sdyx[VEC] = {0.f};
-  for (long long row = (long long)blockIdx.x * rows_per_iter + rsub;
-       row < rows; row += rstride) {
-    const long long off = row * C + (long long)lane * VEC;
+  for (long long row = t.first_row(); row < rows; row += t.rstride) {
+    const long long off = t.off(row);
     BVec g = load8(dz + off);
     BVec xv = load8(x + off);
     BVec dyv;
@@ -625,31 +553,7 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_rm_kernel(
     }
     if (WRITE_DY) store8(dym + off, dyv);
   }
-
-  __shared__ float lds[256 * 2 * VEC];
-  float* mys = &lds[(rsub * lanes + lane) * 2 * VEC];
-#pragma unroll
-  for (int j = 0; j < VEC; ++j) {
-    mys[j] = sdy[j];
-    mys[VEC + j] = sdyx[j];
-  }
-  __syncthreads();
-  for (int step = rows_per_iter >> 1; step > 0; step >>= 1) {
-    if (rsub < step) {
-      const float* other = &lds[((rsub + step) * lanes + lane) * 2 * VEC];
-#pragma unroll
-      for (int j = 0; j < 2 * VEC; ++j) mys[j] += other[j];
-    }
-    __syncthreads();
-  }
-  if (rsub == 0) {
-#pragma unroll
-    for (int j = 0; j < VEC; ++j) {
-      partial[(long long)(lane * VEC + j) * gridDim.x + blockIdx.x] = mys[j];
-      partial[(long long)(C + lane * VEC + j) * gridDim.x + blockIdx.x] =
-          mys[VEC + j];
-    }
-  }
+  block_reduce_store(t, sdy, sdyx, partial);
 }
 
 __global__ __launch_bounds__(256) void bn_bwd_apply_rm_kernel(
@@ -657,28 +561,19 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_rm_kernel(
     const float* __restrict__ mean, const float* __restrict__ invstd,
     const float* __restrict__ bias, const float* __restrict__ k,
     bf16* __restrict__ dx, long long rows, int C) {
-  const int lanes = C / VEC;
-  const int lane = threadIdx.x % lanes;
-  const int rsub = threadIdx.x / lanes;
-  const int rows_per_iter = blockDim.x / lanes;
-  const long long rstride = (long long)gridDim.x * rows_per_iter;
-
+  RowMap t(C);
+  t.span(blockDim.x);
   float m[VEC], is[VEC], wis[VEC], k1[VEC], k2[VEC], bv[VEC], wv[VEC];
+  load_stats(t, mean, invstd, m, is);
+  load_k(t, k, wis, k1, k2);
 #pragma unroll
   for (int j = 0; j < VEC; ++j) {
-    int c = lane * VEC + j;
-    m[j] = mean[c];
-    is[j] = invstd[c];
-    wis[j] = k[c];          // w * invstd
-    k1[j] = k[C + c];
-    k2[j] = k[2 * C + c];
-    bv[j] = bias[c];
+    bv[j] = bias[t.lane * VEC + j];
     wv[j] = wis[j] / is[j];  // w, recovered once per channel
   }
 
-  for (long long row = (long long)blockIdx.x * rows_per_iter + rsub;
-       row < rows; row += rstride) {
-    const long long off = row * C + (long long)lane * VEC;
+  for (long long row = t.first_row(); row < rows; row += t.rstride) {
+    const long long off = t.off(row);
     BVec g = load8(dz + off);
     BVec xv = load8(x + off);
     BVec odx;
@@ -796,68 +691,32 @@ __global__ __launch_bounds__(256) void bn_pool_bwd_reduce_kernel(
     const float* __restrict__ invstd, const float* __restrict__ weight,
     const float* __restrict__ bias, float* __restrict__ partial, int N,
     int H, int W, int Ho, int Wo, int C) {
-  const int lanes = C / VEC;
-  const int lane = threadIdx.x % lanes;
-  const int rsub = threadIdx.x / lanes;
-  const int rows_per_iter = blockDim.x / lanes;
   const long long tiles = (long long)N * Ho * Wo;
-  const long long rstride = (long long)gridDim.x * rows_per_iter;
-
+  RowMap t(C);
+  t.span(blockDim.x);
   float m[VEC], is[VEC], wv[VEC], bv[VEC];
-#pragma unroll
-  for (int j = 0; j < VEC; ++j) {
-    int c = lane * VEC + j;
-    m[j] = mean[c];
-    is[j] = invstd[c];
-    wv[j] = weight[c];
-    bv[j] = bias[c];
-  }
+  load_stats(t, mean, invstd, weight, bias, m, is, wv, bv);
 
   float sdy[VEC] = {0.f}, sdyx[VEC] = {0.f};
-  for (long long row = (long long)blockIdx.x * rows_per_iter + rsub;
-       row < tiles; row += rstride) {
-    PoolTile t;
-    unpool_tile(dp, code, (int)row, lane, H, W, Ho, Wo, C, t);
+  for (long long tile = t.first_row(); tile < tiles; tile += t.rstride) {
+    PoolTile pt;
+    unpool_tile(dp, code, (int)tile, t.lane, H, W, Ho, Wo, C, pt);
     BVec xv[4];
 #pragma unroll
     for (int p = 0; p < 4; ++p)
-      if (t.valid[p]) xv[p] = load8(x + t.pix[p]);
+      if (pt.valid[p]) xv[p] = load8(x + pt.pix[p]);
 #pragma unroll
     for (int p = 0; p < 4; ++p) {
-      if (!t.valid[p]) continue;
+      if (!pt.valid[p]) continue;
 #pragma unroll
       for (int j = 0; j < VEC; ++j) {
         float xhat = (__bfloat162float(xv[p].h[j]) - m[j]) * is[j];
-        float dy = rm_masked_dy(t.a[p][j], wv[j], xhat, bv[j]);
+        float dy = rm_masked_dy(pt.a[p][j], wv[j], xhat, bv[j]);
         rm_accumulate(dy, xhat, sdy[j], sdyx[j]);
       }
     }
   }
-
-  __shared__ float lds[256 * 2 * VEC];
-  float* mys = &lds[(rsub * lanes + lane) * 2 * VEC];
-#pragma unroll
-  for (int j = 0; j < VEC; ++j) {
-    mys[j] = sdy[j];
-    mys[VEC + j] = sdyx[j];
-  }
-  __syncthreads();
-  for (int step = rows_per_iter >> 1; step > 0; step >>= 1) {
-    if (rsub < step) {
-      const float* other = &lds[((rsub + step) * lanes + lane) * 2 * VEC];
-#pragma unroll
-      for (int j = 0; j < 2 * VEC; ++j) mys[j] += other[j];
-    }
-    __syncthreads();
-  }
-  if (rsub == 0) {
-#pragma unroll
-    for (int j = 0; j < VEC; ++j) {
-      partial[(long long)(lane * VEC + j) * gridDim.x + blockIdx.x] = mys[j];
-      partial[(long long)(C + lane * VEC + j) * gridDim.x + blockIdx.x] =
-          mys[VEC + j];
-    }
-  }
+  block_reduce_store(t, sdy, sdyx, partial);
 }
 
 // Arithmetic is bn_bwd_apply_rm_kernel's (the shared rm_* helpers, and
@@ -869,68 +728,61 @@ __global__ __launch_bounds__(256) void bn_pool_bwd_apply_kernel(
     const float* __restrict__ invstd, const float* __restrict__ bias,
     const float* __restrict__ k, bf16* __restrict__ dx, int N, int H, int W,
     int Ho, int Wo, int C) {
-  const int lanes = C / VEC;
-  const int lane = threadIdx.x % lanes;
-  const int rsub = threadIdx.x / lanes;
-  const int rows_per_iter = blockDim.x / lanes;
   const long long tiles = (long long)N * Ho * Wo;
-  const long long rstride = (long long)gridDim.x * rows_per_iter;
-
+  RowMap t(C);
+  t.span(blockDim.x);
   float m[VEC], is[VEC], wis[VEC], k1[VEC], k2[VEC], bv[VEC], wv[VEC];
+  load_stats(t, mean, invstd, m, is);
+  load_k(t, k, wis, k1, k2);
 #pragma unroll
   for (int j = 0; j < VEC; ++j) {
-    int c = lane * VEC + j;
-    m[j] = mean[c];
-    is[j] = invstd[c];
-    wis[j] = k[c];          // w * invstd
-    k1[j] = k[C + c];
-    k2[j] = k[2 * C + c];
-    bv[j] = bias[c];
+    bv[j] = bias[t.lane * VEC + j];
     wv[j] = wis[j] / is[j];  // w, recovered once per channel
   }
 
-  for (long long row = (long long)blockIdx.x * rows_per_iter + rsub;
-       row < tiles; row += rstride) {
-    PoolTile t;
-    unpool_tile(dp, code, (int)row, lane, H, W, Ho, Wo, C, t);
+  for (long long tile = t.first_row(); tile < tiles; tile += t.rstride) {
+    PoolTile pt;
+    unpool_tile(dp, code, (int)tile, t.lane, H, W, Ho, Wo, C, pt);
     BVec xv[4];
 #pragma unroll
     for (int p = 0; p < 4; ++p)
-      if (t.valid[p]) xv[p] = load8(x + t.pix[p]);
+      if (pt.valid[p]) xv[p] = load8(x + pt.pix[p]);
 #pragma unroll
     for (int p = 0; p < 4; ++p) {
-      if (!t.valid[p]) continue;
+      if (!pt.valid[p]) continue;
       BVec odx;
 #pragma unroll
       for (int j = 0; j < VEC; ++j) {
         float xhat = (__bfloat162float(xv[p].h[j]) - m[j]) * is[j];
-        float dy = rm_masked_dy(t.a[p][j], wv[j], xhat, bv[j]);
+        float dy = rm_masked_dy(pt.a[p][j], wv[j], xhat, bv[j]);
         float v = rm_dx(wis[j], dy, k1[j], xhat, k2[j]);
         odx.h[j] = __float2bfloat16(v);
       }
-      store8(dx + t.pix[p], odx);
+      store8(dx + pt.pix[p], odx);
     }
   }
 }
 
 // ------------------------------------------------------------------ launchers
 
-static int pick_grid(long long rows, int C) {
-  // one block advances 256/(C/8) rows per iteration; cap so small
-  // late-layer maps don't launch empty blocks.
+// One block advances 256/(C/8) rows per iteration; enough blocks to cover
+// the rows once, up to `cap`, so small late-layer maps don't launch empty
+// blocks.
+static int grid_blocks(long long rows, int C, long long cap) {
   int rows_per_iter = 256 / (C / VEC);
   long long blocks = (rows + rows_per_iter - 1) / rows_per_iter;
-  if (blocks > 2080) blocks = 2080;  // 8.1 per CU; multiple of 8 XCDs + 1
+  if (blocks > cap) blocks = cap;
   return (int)(blocks > 0 ? blocks : 1);
+}
+
+static int pick_grid(long long rows, int C) {
+  return grid_blocks(rows, C, 2080);  // 8.1 per CU; multiple of 8 XCDs + 1
 }
 
 // Reduce grids are capped lower: 512 blocks (2/CU) saturate HBM on a
 // pure-read pass and bound the partial buffer at 512*2C floats.
 extern "C" int bn_reduce_blocks(long long rows, int C) {
-  int rows_per_iter = 256 / (C / VEC);
-  long long blocks = (rows + rows_per_iter - 1) / rows_per_iter;
-  if (blocks > 512) blocks = 512;
-  return (int)(blocks > 0 ? blocks : 1);
+  return grid_blocks(rows, C, 512);
 }
 
 extern "C" void launch_bn_fwd_reduce(const void* x, float* partial,
@@ -984,39 +836,26 @@ extern "C" void launch_bn_fwd_apply(const void* x, const void* res, void* y,
 #undef APPLY
 }
 
-extern "C" void launch_bn_bwd_reduce(const void* dz, const void* y,
-                                     const void* x, const float* mean,
-                                     const float* invstd, float* partial,
-                                     void* dym, int nblocks, long long rows,
-                                     int C, int relu, hipStream_t stream) {
+// dz2 non-null selects the joined form (dz + dz2 summed in the kernel),
+// which always writes dym.
+extern "C" void launch_bn_bwd_reduce(const void* dz, const void* dz2,
+                                     const void* y, const void* x,
+                                     const float* mean, const float* invstd,
+                                     float* partial, void* dym, int nblocks,
+                                     long long rows, int C, int relu,
+                                     hipStream_t stream) {
   dim3 grid(nblocks), block(256);
-#define REDUCE(R, W)                                                       \
-  hipLaunchKernelGGL((bn_bwd_reduce_kernel<R, W>), grid, block, 0, stream, \
-                     (const bf16*)dz, (const bf16*)y, (const bf16*)x,      \
-                     mean, invstd, partial, (bf16*)dym, rows, C)
-  if (relu && dym) REDUCE(true, true);
-  else if (relu) REDUCE(true, false);
-  else if (dym) REDUCE(false, true);
-  else REDUCE(false, false);
-#undef REDUCE
-}
-
-// Joined form: dz1 + dz2 summed in the kernel; dym is always written.
-extern "C" void launch_bn_bwd_reduce_join(const void* dz1, const void* dz2,
-                                          const void* y, const void* x,
-                                          const float* mean,
-                                          const float* invstd,
-                                          float* partial, void* dym,
-                                          int nblocks, long long rows, int C,
-                                          int relu, hipStream_t stream) {
-  dim3 grid(nblocks), block(256);
-#define REDUCE(R)                                                         \
-  hipLaunchKernelGGL((bn_bwd_reduce_join_kernel<R>), grid, block, 0,      \
-                     stream, (const bf16*)dz1, (const bf16*)dz2,          \
+#define REDUCE(R, W, J)                                                   \
+  hipLaunchKernelGGL((bn_bwd_reduce_kernel<R, W, J>), grid, block, 0,     \
+                     stream, (const bf16*)dz, (const bf16*)dz2,           \
                      (const bf16*)y, (const bf16*)x, mean, invstd,        \
                      partial, (bf16*)dym, rows, C)
-  if (relu) REDUCE(true);
-  else REDUCE(false);
+  if (dz2 && relu) REDUCE(true, true, true);
+  else if (dz2) REDUCE(false, true, true);
+  else if (relu && dym) REDUCE(true, true, false);
+  else if (relu) REDUCE(true, false, false);
+  else if (dym) REDUCE(false, true, false);
+  else REDUCE(false, false, false);
 #undef REDUCE
 }
 
@@ -1074,16 +913,6 @@ extern "C" void launch_bn_pool_bwd_apply(
                      invstd, bias, k, (bf16*)dx, N, H, W, Ho, Wo, C);
 }
 
-extern "C" void launch_bn_bwd_apply_dym(const void* dym, const void* x,
-                                        const float* mean,
-                                        const float* invstd, const float* k,
-                                        void* dx, long long rows, int C,
-                                        hipStream_t stream) {
-  hipLaunchKernelGGL(bn_bwd_apply_dym_kernel, dim3(pick_grid(rows, C)),
-                     dim3(256), 0, stream, (const bf16*)dym, (const bf16*)x,
-                     mean, invstd, k, (bf16*)dx, rows, C);
-}
-
 extern "C" void launch_bn_bwd_finalize(const float* partial, int nblocks,
                                        const float* invstd,
                                        const float* weight, float* dweight,
@@ -1110,4 +939,15 @@ extern "C" void launch_bn_bwd_apply(const void* dz, const void* y,
   else if (dres) APPLY(false, true);
   else APPLY(false, false);
 #undef APPLY
+}
+
+// Residual layers' second pass: dym is already masked and doubles as the
+// residual gradient, so this is the plain apply with no y and no dres.
+extern "C" void launch_bn_bwd_apply_dym(const void* dym, const void* x,
+                                        const float* mean,
+                                        const float* invstd, const float* k,
+                                        void* dx, long long rows, int C,
+                                        hipStream_t stream) {
+  launch_bn_bwd_apply(dym, nullptr, x, mean, invstd, k, dx, nullptr, rows, C,
+                      0, stream);
 }

@@ -14,33 +14,31 @@ composition below doubles as the numerics reference used by the tests.
 State-dict layout matches ``nn.BatchNorm2d`` (weight, bias, running_mean,
 running_var, num_batches_tracked) so checkpoints interoperate.
 
-Round 2: the non-residual relu backward recomputes its mask as
-``(w*xhat + b) > 0`` from the saved x (``bn_bwd_*_rm`` kernels) — the
-stored y is read by NEITHER backward pass and is not saved; and the
-stem's ``forward_pooled`` folds the affine+relu into the maxpool window
-reads so the normalized stem map is never materialized at all.
+Passes and kernels the HIP path leaves out:
 
-Round 3: the stem backward no longer materializes the un-pooled gradient
-map either — ``bn_pool_bwd_reduce`` / ``bn_pool_bwd_apply`` rebuild it in
-registers from the pooled grad and the u8 window codes
-(``MI355X_BN_POOL_FUSED_BWD=0`` selects the three-kernel path for A/B);
-and on the HIP training path ``bn_fwd_finalize`` bumps
-``num_batches_tracked`` on the device, so no per-BN ``+= 1`` kernel runs.
-
-Round 4: ``forward_pooled`` accepts the per-block channel sums the stem
-conv's epilogue already produced (``StemConv2d.forward_with_stats``) and
-then skips ``bn_fwd_reduce``: the 340 MB stem map is not read back for its
-statistics.
-
-Round 5: a residual layer's output is a block output and has two
-consumers (the next block's conv1, and its identity path or downsample
-conv). On the HIP training path ``_FusedBNFn`` returns that output twice
-over one storage; ``BasicBlock`` / ``Bottleneck`` feed one path from each,
-so backward receives the two gradients unsummed and ``bn_bwd_reduce_join``
-adds them while it streams (bf16-rounded, bit-identical to autograd's
-add), and the stand-alone add of two activation-size maps per block no
-longer runs. ``MI355X_BN_JOIN=0`` selects the single-output path for A/B
-runs and tests; ``FusedBNReLU2d.join_calls`` counts joined backwards.
+* Non-residual relu layers recompute the relu mask in backward as
+  ``(w*xhat + b) > 0`` from the saved x (``bn_bwd_*_rm``): the stored y is
+  read by neither backward pass and is not saved.
+* Residual layers' outputs are block outputs with two consumers (the next
+  block's conv1, and its identity path or downsample conv). In training
+  ``_FusedBNFn`` returns that output twice over one storage; ``BasicBlock``
+  / ``Bottleneck`` feed one path from each, so backward receives the two
+  gradients unsummed and the joined ``bn_bwd_reduce`` adds them while it
+  streams (bf16-rounded, bit-identical to autograd's add): the stand-alone
+  add of two activation-size maps per block does not run.
+  ``MI355X_BN_JOIN=0`` selects the single-output path for A/B runs and
+  tests; ``FusedBNReLU2d.join_calls`` counts joined backwards.
+* The stem (``forward_pooled``) folds affine+relu into the max-pool window
+  reads, so the normalized stem map is never materialized; it accepts the
+  per-block channel sums the stem conv's epilogue already produced
+  (``StemConv2d.forward_with_stats``) and then skips ``bn_fwd_reduce``, so
+  the 340 MB stem map is not read back for its statistics. Its backward
+  rebuilds the un-pooled gradient in registers from the pooled gradient
+  and the u8 window codes (``bn_pool_bwd_*``);
+  ``MI355X_BN_POOL_FUSED_BWD=0`` selects the three-kernel path for A/B.
+* ``bn_fwd_finalize`` bumps ``num_batches_tracked`` on the device, so no
+  per-BN ``+= 1`` kernel runs; inside hipGraph capture ``bn_bwd_finalize``
+  accumulates straight into the flat grad views (``MI355X_BN_FUSED_ACC``).
 
 All device work is stream-ordered with no host sync, so the op captures
 into hipGraphs (train/graphstep.py).
@@ -64,6 +62,34 @@ def _hip_supported(x: torch.Tensor) -> bool:
     c = x.shape[1]
     return (x.is_cuda and x.dtype == torch.bfloat16 and x.dim() == 4
             and c % 8 == 0 and c <= 2048 and (256 % (c // 8)) == 0)
+
+
+def _channel_grads(weight, bias, C, dev):
+    """Where ``bn_bwd_finalize`` puts dweight/dbias: ``(dweight, dbias,
+    fuse_acc)``.
+
+    Inside hipGraph capture (the flagship graphed step) the kernel
+    accumulates straight into the existing flat grad views and backward
+    returns None for weight/bias — autograd's per-param AccumulateGrad adds
+    (~40 launch-bound kernels/step across the model's BNs) vanish from the
+    captured graph. Outside capture (eager, DDP hooks, tests with fresh
+    .grad) fresh buffers keep the standard return-grads contract.
+    """
+    def _grad_view(p):
+        g = p.grad
+        if (g is not None and g.is_cuda and g.is_contiguous()
+                and g.dtype == torch.float32 and g.numel() == C):
+            return g
+        return None
+
+    wg, bg = _grad_view(weight), _grad_view(bias)
+    fuse_acc = (torch.cuda.is_current_stream_capturing()
+                and wg is not None and bg is not None
+                and os.environ.get("MI355X_BN_FUSED_ACC", "1") == "1")
+    if fuse_acc:
+        return wg, bg, True
+    return (torch.empty(C, dtype=torch.float32, device=dev),
+            torch.empty(C, dtype=torch.float32, device=dev), False)
 
 
 class _FusedBNFn(torch.autograd.Function):
@@ -103,7 +129,6 @@ class _FusedBNFn(torch.autograd.Function):
         x, y, mean, invstd, weight, bias = ctx.saved_tensors
         C = x.shape[1]
         rows = x.numel() // C
-        dev = x.device
         if dz is None:
             dz, dz2 = dz2, None
         if dz is None:  # joined forward, neither output used
@@ -113,32 +138,11 @@ class _FusedBNFn(torch.autograd.Function):
         if (dz2 is not None and
                 not dz2.is_contiguous(memory_format=torch.channels_last)):
             dz2 = dz2.contiguous(memory_format=torch.channels_last)
-        k = torch.empty(3 * C, dtype=torch.float32, device=dev)
-        # Inside hipGraph capture (the flagship graphed step), write the
-        # channel grads straight into the existing flat grad views and
-        # return None for weight/bias — autograd's per-param
-        # AccumulateGrad adds (~40 launch-bound kernels/step across the
-        # model's BNs) vanish from the captured graph. Outside capture
-        # (eager, DDP hooks, tests with fresh .grad) keep the standard
-        # return-grads contract.
-        def _grad_view(p):
-            g = p.grad
-            if (g is not None and g.is_cuda and g.is_contiguous()
-                    and g.dtype == torch.float32 and g.numel() == C):
-                return g
-            return None
-
-        import os
-        wg, bg = _grad_view(weight), _grad_view(bias)
-        fuse_acc = (torch.cuda.is_current_stream_capturing()
-                    and wg is not None and bg is not None
-                    and os.environ.get("MI355X_BN_FUSED_ACC", "1") == "1")
-        if fuse_acc:
-            dweight, dbias = wg, bg
-        else:
-            dweight = torch.empty(C, dtype=torch.float32, device=dev)
-            dbias = torch.empty(C, dtype=torch.float32, device=dev)
+        k = torch.empty(3 * C, dtype=torch.float32, device=x.device)
+        dweight, dbias, fuse_acc = _channel_grads(weight, bias, C, x.device)
         dx = torch.empty_like(x)
+        dym = None
+        # reduce
         if ctx.has_res:
             # residual layer: the reduce pass materializes the masked
             # upstream grad (dym) which IS the residual gradient; the
@@ -154,32 +158,31 @@ class _FusedBNFn(torch.autograd.Function):
             else:
                 partial = _C.bn_bwd_reduce(dz, y, x, mean, invstd, dym, C,
                                            ctx.relu)
-            _C.bn_bwd_finalize(partial, invstd, weight, dweight, dbias, k,
-                               rows, C, fuse_acc)
+        else:
+            # only residual layers are joined in forward
+            assert dz2 is None
+            if ctx.relu:
+                # recompute-mask path: one full activation-map read (the
+                # stored y) drops out of BOTH backward passes
+                partial = _C.bn_bwd_reduce_rm(dz, x, mean, invstd, weight,
+                                              bias, x.new_empty(0), C)
+            else:
+                partial = _C.bn_bwd_reduce(dz, y, x, mean, invstd,
+                                           x.new_empty(0), C, False)
+        _C.bn_bwd_finalize(partial, invstd, weight, dweight, dbias, k, rows,
+                           C, fuse_acc)
+        # apply
+        if ctx.has_res:
             _C.bn_bwd_apply_dym(dym, x, mean, invstd, k, dx, C)
-            return (dx, dym, None if fuse_acc else dweight,
-                    None if fuse_acc else dbias, None, None, None, None,
-                    None, None, None)
-        # only residual layers are joined in forward
-        assert dz2 is None
-        if ctx.relu:
-            # recompute-mask path: one full activation-map read (the
-            # stored y) drops out of BOTH backward passes
-            partial = _C.bn_bwd_reduce_rm(dz, x, mean, invstd, weight,
-                                          bias, x.new_empty(0), C)
-            _C.bn_bwd_finalize(partial, invstd, weight, dweight, dbias, k,
-                               rows, C, fuse_acc)
+        elif ctx.relu:
             _C.bn_bwd_apply_rm(dz, x, mean, invstd, bias, k, dx, C)
         else:
-            partial = _C.bn_bwd_reduce(dz, y, x, mean, invstd,
-                                       x.new_empty(0), C, False)
-            _C.bn_bwd_finalize(partial, invstd, weight, dweight, dbias, k,
-                               rows, C, fuse_acc)
             _C.bn_bwd_apply(dz, y, x, mean, invstd, k, dx, x.new_empty(0),
                             C, False)
-        return (dx, None, None if fuse_acc else dweight,
-                None if fuse_acc else dbias, None, None, None, None, None,
-                None, None)
+        if fuse_acc:  # the kernel already accumulated the channel grads
+            dweight = dbias = None
+        return (dx, dym, dweight, dbias, None, None, None, None, None, None,
+                None)
 
 
 class _FusedBNPoolFn(torch.autograd.Function):
@@ -221,10 +224,8 @@ class _FusedBNPoolFn(torch.autograd.Function):
         x, mean, invstd, weight, bias, code = ctx.saved_tensors
         C = x.shape[1]
         rows = x.numel() // C
-        dev = x.device
         if not dp.is_contiguous(memory_format=torch.channels_last):
             dp = dp.contiguous(memory_format=torch.channels_last)
-        import os
         # Default: the un-pooled map dz is rebuilt in registers inside
         # both BN passes (bn_pool_bwd_* kernels) and never allocated.
         # MI355X_BN_POOL_FUSED_BWD=0 selects the three-kernel path
@@ -233,31 +234,12 @@ class _FusedBNPoolFn(torch.autograd.Function):
         # is built from this tree, and an extension without them must
         # raise rather than quietly run the slower path.
         fused_unpool = os.environ.get("MI355X_BN_POOL_FUSED_BWD", "1") != "0"
-        k = torch.empty(3 * C, dtype=torch.float32, device=dev)
-
-        def _grad_view(p):
-            g = p.grad
-            if (g is not None and g.is_cuda and g.is_contiguous()
-                    and g.dtype == torch.float32 and g.numel() == C):
-                return g
-            return None
-
-        wg, bg = _grad_view(weight), _grad_view(bias)
-        fuse_acc = (torch.cuda.is_current_stream_capturing()
-                    and wg is not None and bg is not None
-                    and os.environ.get("MI355X_BN_FUSED_ACC", "1") == "1")
-        if fuse_acc:
-            dweight, dbias = wg, bg
-        else:
-            dweight = torch.empty(C, dtype=torch.float32, device=dev)
-            dbias = torch.empty(C, dtype=torch.float32, device=dev)
+        k = torch.empty(3 * C, dtype=torch.float32, device=x.device)
+        dweight, dbias, fuse_acc = _channel_grads(weight, bias, C, x.device)
         dx = torch.empty_like(x)
         if fused_unpool:
             partial = _C.bn_pool_bwd_reduce(dp, code, x, mean, invstd,
                                             weight, bias)
-            _C.bn_bwd_finalize(partial, invstd, weight, dweight, dbias, k,
-                               rows, C, fuse_acc)
-            _C.bn_pool_bwd_apply(dp, code, x, mean, invstd, bias, k, dx)
         else:
             # un-pool: scatter the pooled grad to the argmax positions,
             # then the recompute-mask BN backward (fused_bn.hip rm kernels)
@@ -265,12 +247,15 @@ class _FusedBNPoolFn(torch.autograd.Function):
             _C.maxpool3x3s2_bwd(dp, code, dz)
             partial = _C.bn_bwd_reduce_rm(dz, x, mean, invstd, weight, bias,
                                           x.new_empty(0), C)
-            _C.bn_bwd_finalize(partial, invstd, weight, dweight, dbias, k,
-                               rows, C, fuse_acc)
+        _C.bn_bwd_finalize(partial, invstd, weight, dweight, dbias, k, rows,
+                           C, fuse_acc)
+        if fused_unpool:
+            _C.bn_pool_bwd_apply(dp, code, x, mean, invstd, bias, k, dx)
+        else:
             _C.bn_bwd_apply_rm(dz, x, mean, invstd, bias, k, dx, C)
-        return (dx, None if fuse_acc else dweight,
-                None if fuse_acc else dbias, None, None, None, None, None,
-                None, None)
+        if fuse_acc:  # the kernel already accumulated the channel grads
+            dweight = dbias = None
+        return (dx, dweight, dbias, None, None, None, None, None, None, None)
 
 
 class FusedBNReLU2d(nn.Module):
@@ -355,7 +340,7 @@ class FusedBNReLU2d(nn.Module):
                 # still get ONE tensor; it carries a second autograd output
                 # over the same storage, and a block that feeds one path
                 # from each (models/resnet.py) gets its two gradients
-                # summed inside bn_bwd_reduce_join instead of by a
+                # summed inside the joined bn_bwd_reduce instead of by a
                 # stand-alone add kernel. A caller that ignores the twin
                 # behaves as before. The returned tensor is the view and
                 # holds the base, not the other way round: a base that held
