@@ -5,6 +5,7 @@
 #include <ATen/hip/HIPContext.h>
 #include <c10/hip/HIPException.h>
 #include <hip/hip_runtime.h>
+#include <cstdint>
 #include <cstdlib>
 
 extern "C" void launch_normalize_u8_to_bf16(
@@ -739,6 +740,16 @@ extern "C" void launch_adam_step(float* p, const float* g, float* m,
                                  float beta2, float eps, float weight_decay,
                                  long long n, hipStream_t stream);
 
+// The Adam kernels read and write 4-element packs from element 0 of each
+// buffer: 16 B for fp32, 8 B for bf16. A view that starts off that
+// alignment is rejected here, before any launch.
+static void _check_adam_align(const torch::Tensor& t, size_t bytes,
+                              const char* name) {
+  TORCH_CHECK(t.numel() == 0 ||
+                  reinterpret_cast<uintptr_t>(t.data_ptr()) % bytes == 0,
+              name, " must be ", bytes, "-byte aligned");
+}
+
 // One fused Adam step over the flat fp32 param/grad/moment buffers.
 // step: int32 device scalar (bumped on-device; hipGraph-replayable).
 void adam_step(torch::Tensor p, torch::Tensor g, torch::Tensor m,
@@ -752,6 +763,8 @@ void adam_step(torch::Tensor p, torch::Tensor g, torch::Tensor m,
   long long n = p.numel();
   TORCH_CHECK(g.numel() == n && m.numel() == n && v.numel() == n,
               "flat buffer length mismatch");
+  _check_adam_align(p, 16, "p"); _check_adam_align(g, 16, "g");
+  _check_adam_align(m, 16, "m"); _check_adam_align(v, 16, "v");
   launch_adam_step(p.data_ptr<float>(), g.data_ptr<float>(),
                    m.data_ptr<float>(), v.data_ptr<float>(),
                    step.data_ptr<int>(), (float)lr, (float)beta1,
@@ -777,12 +790,18 @@ void adam_step_mixed(torch::Tensor master, torch::Tensor gb,
   _check_f32(master, "master"); _check_f32(m, "m"); _check_f32(v, "v");
   TORCH_CHECK(gb.scalar_type() == torch::kBFloat16 &&
               pb.scalar_type() == torch::kBFloat16, "gb/pb must be bf16");
+  TORCH_CHECK(gb.is_cuda() && gb.is_contiguous() && pb.is_cuda() &&
+              pb.is_contiguous(), "gb/pb must be contiguous on GPU");
+  if (gf.numel()) _check_f32(gf, "gf");
   TORCH_CHECK(step.is_cuda() && step.scalar_type() == torch::kInt32 &&
               step.numel() == 1, "step must be int32[1] on device");
   long long n = master.numel();
   long long nb = gb.numel();
   TORCH_CHECK(pb.numel() == nb && gf.numel() == n - nb &&
               m.numel() == n && v.numel() == n, "buffer length mismatch");
+  _check_adam_align(master, 16, "master"); _check_adam_align(m, 16, "m");
+  _check_adam_align(v, 16, "v"); _check_adam_align(gf, 16, "gf");
+  _check_adam_align(gb, 8, "gb"); _check_adam_align(pb, 8, "pb");
   launch_adam_step_mixed(master.data_ptr<float>(), gb.data_ptr(),
                          _f32_or_null(gf),
                          m.data_ptr<float>(), v.data_ptr<float>(),
