@@ -25,6 +25,13 @@ Yule-Walker/Levinson for the long-AR stage):
 the numerics oracle for the HIP kernel (``ops/csrc/groupfit.hip``), which
 runs one group per lane, 64 groups per wave, series slabs in LDS,
 time-major [T, G] global layout for coalescing.
+
+Out-of-sample: ``forecast_from_params_reference`` /
+``batched_forecast_reference`` define the H-step forecast, the innovation
+variance and the psi-weight standard errors; ``batched_forecast_gpu``
+(``groupfit_forecast_kernel``) computes them for a whole panel from the
+stored ``params`` / ``best_order``, and ``batched_fit_gpu(...,
+future_exog=F)`` fits and forecasts in one call.
 """
 from __future__ import annotations
 
@@ -302,14 +309,85 @@ def batched_eval_gpu(y, exog, orders, train_len: int, device="cuda",
     return mse.t().contiguous(), status.t().contiguous()
 
 
+def _check_future_exog(exog, future_exog, T: int) -> int:
+    """Host-side shape checks shared by the forecast entry points; returns
+    the horizon H."""
+    ex, fx = np.shape(exog), np.shape(future_exog)
+    if len(ex) != 2 or ex[0] != T:
+        raise ValueError(f"exog must have T = {T} rows, got shape {ex}")
+    if len(fx) != 2 or fx[1] != ex[1]:
+        raise ValueError(f"future_exog must be [H, {ex[1]}] like exog, "
+                         f"got shape {fx}")
+    if fx[0] < 1:
+        raise ValueError("future_exog needs at least one row (H >= 1)")
+    return int(fx[0])
+
+
+def _forecast_launch(yT, xs, best_order, params, H: int):
+    """``groupfit_forecast`` on device tensors; ``xs`` are the stacked
+    designs. Returns forecast/forecast_se [G,H], sigma2/status [G]."""
+    import torch
+    from ..ops import _C
+    T, G = yT.shape
+    dev = yT.device
+    forecast = torch.empty((H, G), dtype=torch.float32, device=dev)
+    forecast_se = torch.empty((H, G), dtype=torch.float32, device=dev)
+    sigma2 = torch.empty((G,), dtype=torch.float32, device=dev)
+    status = torch.empty((G,), dtype=torch.uint8, device=dev)
+    _C.groupfit_forecast(yT, xs[0], xs[1], xs[2], best_order, params,
+                         forecast, forecast_se, sigma2, status)
+    return {"forecast": forecast.t().contiguous(),
+            "forecast_se": forecast_se.t().contiguous(),
+            "sigma2": sigma2, "status": status}
+
+
+def batched_forecast_gpu(y, exog, future_exog, best_order, params,
+                         device="cuda"):
+    """Out-of-sample forecast from STORED coefficients: ``params``
+    [G,1+KX+8] and ``best_order`` [G,3] as ``batched_fit_gpu`` returned
+    them for the same ``y`` [G,T] and ``exog`` [T,KX]. No fitting: one
+    streaming pass rebuilds the end-of-series state, then
+    ``H = len(future_exog)`` steps. Returns a dict with ``forecast``
+    [G,H], ``forecast_se`` [G,H], ``sigma2`` [G] and ``status`` [G] (1 iff
+    every output of the group is finite)."""
+    ys = np.shape(y)
+    if len(ys) != 2:
+        raise ValueError(f"y must be [G, T], got shape {ys}")
+    G, T = ys
+    H = _check_future_exog(exog, future_exog, T)
+    KX = np.shape(exog)[1]
+    if tuple(np.shape(params)) != (G, 1 + KX + 8):
+        raise ValueError(f"params must be [{G}, {1 + KX + 8}], got shape "
+                         f"{tuple(np.shape(params))}")
+    if tuple(np.shape(best_order)) != (G, 3):
+        raise ValueError(f"best_order must be [{G}, 3], got shape "
+                         f"{tuple(np.shape(best_order))}")
+    import torch
+    from ..ops import require_ext
+    require_ext()
+    yT = _to_yT(y, device)
+    xs, _ = _designs_to_gpu(stacked_exog_designs(exog, future_exog, T),
+                            device)
+    best_order = torch.as_tensor(best_order).to(
+        device=device, dtype=torch.int32).contiguous()
+    params = torch.as_tensor(params).to(
+        device=device, dtype=torch.float32).contiguous()
+    return _forecast_launch(yT, xs, best_order, params, H)
+
+
 def batched_fit_gpu(y, exog, orders, train_len: int, device="cuda",
-                    use_mfma: bool = True):
+                    use_mfma: bool = True, future_exog=None):
     """Full W1 GPU pipeline: evaluate candidates, pick the best per group,
     final-fit on the whole series. Returns a dict with ``best_order``
     [G,3], ``mse`` [G,C], ``fitted`` [G,T], ``params`` [G,1+KX+8],
-    ``status`` [G] (all torch tensors on ``device``)."""
+    ``status`` [G] (all torch tensors on ``device``). With ``future_exog``
+    [H,KX] the final fit is followed by an H-step forecast from its
+    coefficients: ``forecast`` [G,H], ``forecast_se`` [G,H], ``sigma2``
+    [G] and ``forecast_status`` [G] are added, the other keys unchanged."""
     import torch
     from ..ops import require_ext, _C
+    if future_exog is not None:
+        H = _check_future_exog(exog, future_exog, np.shape(y)[1])
     require_ext()
     yT = _to_yT(y, device)
     T, G = yT.shape
@@ -319,7 +397,11 @@ def batched_fit_gpu(y, exog, orders, train_len: int, device="cuda",
                             ).reshape(-1, 3)
     best_ci = mse.argmin(dim=1)                        # [G]
     best_order = orders_t[best_ci].contiguous()        # [G,3]
-    designs = make_exog_designs(exog, T)               # full-series designs
+    if future_exog is None:
+        designs = make_exog_designs(exog, T)           # full-series designs
+    else:
+        # same history rows and P, bit for bit, plus the H future rows
+        designs = stacked_exog_designs(exog, future_exog, T)
     xs, ps = _designs_to_gpu(designs, device)
     KX = xs[0].shape[1]
     if use_mfma:
@@ -337,11 +419,16 @@ def batched_fit_gpu(y, exog, orders, train_len: int, device="cuda",
                       best_order, fitted, params, fstatus,
                       betas[0], betas[1], betas[2],
                       wms[0], wms[1], wms[2])
-    return {
+    out = {
         "best_order": best_order, "mse": mse, "eval_status": status,
         "fitted": fitted.t().contiguous(), "params": params,
         "status": fstatus,
     }
+    if future_exog is not None:
+        fc = _forecast_launch(yT, xs, best_order, params, H)
+        out["forecast_status"] = fc.pop("status")
+        out.update(fc)
+    return out
 
 
 def fitted_values_reference(y: np.ndarray, exog: np.ndarray,
@@ -384,3 +471,128 @@ def fitted_values_reference(y: np.ndarray, exog: np.ndarray,
     else:
         fit[2:] = dt(2.0) * y[1:-1] - y[:-2] + what
     return fit
+
+
+# --------------------------------------------------------------------------
+# out-of-sample forecast with standard errors
+# --------------------------------------------------------------------------
+def stacked_exog_designs(exog: np.ndarray, future_exog: np.ndarray,
+                         train_len: int) -> List[ExogDesign]:
+    """Designs over history + future rows: ``n = train_len - d`` history
+    rows followed by the ``H`` future rows, differenced against the tail
+    of the history and centered with the history means. The first ``n``
+    rows and ``P`` are those of ``make_exog_designs(exog, train_len)``."""
+    return make_exog_designs(
+        np.vstack([np.asarray(exog, dtype=np.float64),
+                   np.asarray(future_exog, dtype=np.float64)]), train_len)
+
+
+def psi_weights_reference(phi: np.ndarray, theta: np.ndarray, d: int,
+                          steps: int, dtype=np.float64) -> np.ndarray:
+    """psi_0..psi_{steps-1} of the ARIMA(p,d,q) process: with
+    ``1 - sum a_k B^k = (1 - sum phi_i B^i)(1 - B)^d``, psi_0 = 1 and
+    ``psi_j = theta_j [j <= q] + sum_{k=1}^{min(j,p+d)} a_k psi_{j-k}``."""
+    dt = np.dtype(dtype).type
+    phi = np.asarray(phi, dtype=dtype)
+    theta = np.asarray(theta, dtype=dtype)
+    p, q = len(phi), len(theta)
+    c = np.zeros(p + d + 1, dtype=dtype)      # 1 - sum a_k B^k
+    c[0] = dt(1.0)
+    c[1:p + 1] = -phi
+    for _ in range(d):                        # times (1 - B)
+        c[1:] = c[1:] - c[:-1]
+    a = -c[1:]
+    psi = np.zeros(steps, dtype=dtype)
+    for j in range(steps):
+        if j == 0:
+            psi[0] = dt(1.0)
+            continue
+        acc = theta[j - 1] if j <= q else dt(0.0)
+        for k in range(1, min(j, p + d) + 1):
+            acc += a[k - 1] * psi[j - k]
+        psi[j] = acc
+    return psi
+
+
+def forecast_from_params_reference(
+        y: np.ndarray, design_d: ExogDesign, order: Tuple[int, int, int],
+        wm, beta: np.ndarray, phi4: np.ndarray, theta4: np.ndarray, H: int,
+        dtype=np.float64) -> Tuple[np.ndarray, np.ndarray, float]:
+    """H-step forecast of one group with the coefficients GIVEN:
+    ``(forecast [H], forecast_se [H], sigma2)``. ``design_d`` is the
+    stacked design of the order's ``d`` (``T - d`` history rows, then H
+    future rows); ``phi4``/``theta4`` are zero past p/q. The residual
+    recursion is the fitted-value pass of ``groupfit_final``; the
+    regression coefficients count as fixed in the standard error."""
+    p, d, q = order
+    dt = np.dtype(dtype).type
+    y = np.asarray(y, dtype=dtype)
+    T = len(y)
+    n = T - d
+    dz = _design_as(design_d, dtype)
+    if dz.Xc_full.shape[0] != n + H:
+        raise ValueError(f"design has {dz.Xc_full.shape[0]} rows, "
+                         f"need {n} + {H}")
+    wm = dt(wm)
+    beta = np.asarray(beta, dtype=dtype)
+    phi4 = np.asarray(phi4, dtype=dtype)
+    theta4 = np.asarray(theta4, dtype=dtype)
+    w = y.copy()
+    for _ in range(d):
+        w = np.diff(w)
+    u = (w - wm) - dz.Xc_full[:n] @ beta
+    e = np.zeros(n, dtype=dtype)
+    m = max(p, q)
+    sse = dt(0.0)
+    for td in range(n):
+        acc = dt(0.0)
+        for i in range(min(4, td)):
+            acc += phi4[i] * u[td - 1 - i] + theta4[i] * e[td - 1 - i]
+        e[td] = u[td] - acc
+        if td >= m:
+            sse += e[td] * e[td]
+    sigma2 = sse / dt(n - m)
+    reg_future = dz.Xc_full[n:n + H] @ beta
+    fc = _forecast_y(y, T, H, d, wm, reg_future, phi4[:p], theta4[:q], u, e,
+                     dtype)
+    psi = psi_weights_reference(phi4[:p], theta4[:q], d, H, dtype)
+    se = np.sqrt(sigma2 * np.cumsum(psi * psi, dtype=dtype))
+    return fc, se, sigma2
+
+
+def batched_forecast_reference(
+        y: np.ndarray, exog: np.ndarray, future_exog: np.ndarray,
+        orders_per_group, dtype=np.float64,
+) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """Fit every group on its whole series (as ``fitted_values_reference``
+    does) and forecast ``len(future_exog)`` steps past it. One order for
+    all groups, or one per group. Returns ``forecast [G,H]``,
+    ``forecast_se [G,H]`` and ``sigma2 [G]`` in ``dtype``."""
+    y = np.asarray(y, dtype=dtype)
+    G, T = y.shape
+    H = len(future_exog)
+    if np.ndim(orders_per_group) == 1:
+        orders_per_group = [tuple(orders_per_group)] * G
+    by_d = {dz.d: dz for dz in stacked_exog_designs(exog, future_exog, T)}
+    fc = np.empty((G, H), dtype=dtype)
+    se = np.empty((G, H), dtype=dtype)
+    s2 = np.empty(G, dtype=dtype)
+    for g in range(G):
+        p, d, q = (int(v) for v in orders_per_group[g])
+        dz = _design_as(by_d[d], dtype)
+        n = T - d
+        w = y[g].copy()
+        for _ in range(d):
+            w = np.diff(w)
+        wm = w.mean()
+        wc = w - wm
+        beta = dz.P @ wc
+        u = wc - dz.Xc_full[:n] @ beta
+        phi, theta, _ = _fit_arma_one(u, p, q, dtype=dtype)
+        phi4 = np.zeros(4, dtype=dtype)
+        theta4 = np.zeros(4, dtype=dtype)
+        phi4[:p] = phi
+        theta4[:q] = theta
+        fc[g], se[g], s2[g] = forecast_from_params_reference(
+            y[g], by_d[d], (p, d, q), wm, beta, phi4, theta4, H, dtype)
+    return fc, se, s2

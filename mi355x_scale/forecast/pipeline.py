@@ -80,12 +80,43 @@ def evaluate_model(params: Dict, train: pd.DataFrame, score: pd.DataFrame,
         return {"loss": None, "status": STATUS_FAIL}
 
 
+def _check_forecast_args(forecast_steps, interval) -> int:
+    """Validate the two forecast keywords; returns the horizon H."""
+    H = int(forecast_steps)
+    if H < 0:
+        raise ValueError(f"forecast_steps must be >= 0, got {forecast_steps}")
+    if interval is not None and not 0.0 < float(interval) < 1.0:
+        raise ValueError(f"interval must be in (0, 1), got {interval}")
+    return H
+
+
+def _future_dates(dates, H: int) -> pd.DatetimeIndex:
+    """H dates past the last one, at the spacing of the last two."""
+    d = pd.DatetimeIndex(pd.to_datetime(dates))
+    return pd.DatetimeIndex(d[-1] + (d[-1] - d[-2]) * np.arange(1, H + 1))
+
+
+def _interval_z(interval: float) -> float:
+    """Two-sided normal quantile: the interval is forecast -/+ z * se."""
+    from statistics import NormalDist
+    return NormalDist().inv_cdf(0.5 + float(interval) / 2.0)
+
+
 def build_tune_and_score_model(sku_pdf: pd.DataFrame,
                                horizon: int = FORECAST_HORIZON,
                                max_evals: int = 10,
-                               seed: int = 123) -> pd.DataFrame:
+                               seed: int = 123,
+                               forecast_steps: int = 0,
+                               interval: Optional[float] = None
+                               ) -> pd.DataFrame:
     """The applyInPandas group function (ref :417-494): returns a frame
-    matching TUNING_SCHEMA with one-step-ahead fitted demand."""
+    matching TUNING_SCHEMA with one-step-ahead fitted demand. With
+    ``forecast_steps > 0`` that many future rows follow (dates continue at
+    the spacing of the last two, Demand is NaN, Demand_Fitted holds the
+    forecast); with ``interval`` in (0,1) the columns Demand_Lower /
+    Demand_Upper hold forecast -/+ z * se on the future rows and NaN on
+    the history rows."""
+    H = _check_forecast_args(forecast_steps, interval)
     pdf = sku_pdf.sort_values("Date").reset_index(drop=True)
     train, score = split_train_score_data(pdf, horizon)
 
@@ -100,14 +131,42 @@ def build_tune_and_score_model(sku_pdf: pd.DataFrame,
     res = SARIMAX(pdf["Demand"].to_numpy(),
                   exog=pdf[EXO_COLS].to_numpy(),
                   order=(p, d, q)).fit(disp=False)
-    fitted = res.predict(0, len(pdf) - 1)
-    return pd.DataFrame({
-        "Product": pdf["Product"],
-        "SKU": pdf["SKU"],
-        "Date": pd.to_datetime(pdf["Date"]),
-        "Demand": pdf["Demand"].astype(float),
+    T = len(pdf)
+    dates = pd.to_datetime(pdf["Date"])
+    demand = pdf["Demand"].astype(float)
+    product, sku = pdf["Product"], pdf["SKU"]
+    if H > 0:
+        fdates = _future_dates(dates, H)
+        future = add_exo_variables(
+            pd.DataFrame({"Date": fdates}))[EXO_COLS].to_numpy()
+        fitted = res.predict(0, T - 1 + H, exog=future)
+        dates = pd.concat([dates, pd.Series(fdates)], ignore_index=True)
+        demand = pd.concat([demand, pd.Series(np.full(H, np.nan))],
+                           ignore_index=True)
+        product = pd.Series([product.iloc[0]] * (T + H))
+        sku = pd.Series([sku.iloc[0]] * (T + H))
+    else:
+        fitted = res.predict(0, T - 1)
+    out = pd.DataFrame({
+        "Product": product,
+        "SKU": sku,
+        "Date": dates,
+        "Demand": demand,
         "Demand_Fitted": fitted,
     })
+    if interval is not None:
+        half = np.full(T + H, np.nan)
+        if H > 0:
+            half[T:] = _interval_z(interval) * res.forecast_se(H)
+        out["Demand_Lower"] = out["Demand_Fitted"] - half
+        out["Demand_Upper"] = out["Demand_Fitted"] + half
+    return out
+
+
+def _forecast_schema(interval) -> str:
+    if interval is None:
+        return TUNING_SCHEMA
+    return TUNING_SCHEMA + ", Demand_Lower float, Demand_Upper float"
 
 
 DEFAULT_GPU_ORDERS = [(0, 1, 0), (1, 0, 0), (1, 1, 0), (0, 1, 1),
@@ -117,14 +176,21 @@ DEFAULT_GPU_ORDERS = [(0, 1, 0), (1, 0, 0), (1, 1, 0), (0, 1, 1),
 
 def run_fine_grained_forecast_gpu(demand_df: pd.DataFrame,
                                   orders=None,
-                                  horizon: int = FORECAST_HORIZON
+                                  horizon: int = FORECAST_HORIZON,
+                                  forecast_steps: int = 0,
+                                  interval: Optional[float] = None
                                   ) -> pd.DataFrame:
     """W1 on the batched CDNA4 kernel: same input/output frames as
     ``run_fine_grained_forecast`` but every group is fitted on the GPU
     (candidate grid -> best-per-group -> final fit), ~10^6 groups/sec.
+    ``forecast_steps`` and ``interval`` as in
+    ``build_tune_and_score_model``: future rows from the forecast kernel,
+    their exogenous indicators from ``add_exo_variables`` on the future
+    dates.
     """
     from ..groupby.gather import long_from_panel, panel_from_long
     from .batched import batched_fit_gpu
+    H = _check_forecast_args(forecast_steps, interval)
     # C++ group gather (the Spark-shuffle replacement): factorize + scatter
     y, gindex, dates = panel_from_long(demand_df, ["Product", "SKU"],
                                        "Date", "Demand")
@@ -133,18 +199,41 @@ def run_fine_grained_forecast_gpu(demand_df: pd.DataFrame,
     exog = add_exo_variables(
         pd.DataFrame({"Date": pd.to_datetime(dates)}))[EXO_COLS].to_numpy()
     T = y.shape[1]
+    future_exog = None
+    if H > 0:
+        fdates = _future_dates(dates, H)
+        future_exog = add_exo_variables(
+            pd.DataFrame({"Date": fdates}))[EXO_COLS].to_numpy()
     out = batched_fit_gpu(y, exog, orders or DEFAULT_GPU_ORDERS,
-                          train_len=T - horizon)
-    fitted = out["fitted"].cpu().numpy()
-    res = long_from_panel(y, gindex, dates, ["Product", "SKU"], "Date",
-                          [("Demand", y.astype(np.float64)),
-                           ("Demand_Fitted", fitted.astype(np.float64))])
+                          train_len=T - horizon, future_exog=future_exog)
+    demand = y.astype(np.float64)
+    fitted = out["fitted"].cpu().numpy().astype(np.float64)
+    cols = ["Product", "SKU", "Date", "Demand", "Demand_Fitted"]
+    if H > 0:
+        G = len(demand)
+        dates = pd.DatetimeIndex(pd.to_datetime(dates)).append(
+            fdates).to_numpy()
+        demand = np.concatenate([demand, np.full((G, H), np.nan)], axis=1)
+        fitted = np.concatenate(
+            [fitted, out["forecast"].cpu().numpy().astype(np.float64)],
+            axis=1)
+    values = [("Demand", demand), ("Demand_Fitted", fitted)]
+    if interval is not None:
+        half = np.full(fitted.shape, np.nan)
+        if H > 0:
+            half[:, T:] = _interval_z(interval) * out[
+                "forecast_se"].cpu().numpy().astype(np.float64)
+        values += [("Demand_Lower", fitted - half),
+                   ("Demand_Upper", fitted + half)]
+        cols += ["Demand_Lower", "Demand_Upper"]
+    res = long_from_panel(demand, gindex, dates, ["Product", "SKU"], "Date",
+                          values)
     if not np.issubdtype(res["Date"].dtype, np.datetime64):
         # tiled tvals are already datetime64 for datetime inputs —
         # an unconditional to_datetime copied 15.7M timestamps (~0.11 s
         # of the 0.72 s end-to-end job) for nothing
         res["Date"] = pd.to_datetime(res["Date"])
-    return res[["Product", "SKU", "Date", "Demand", "Demand_Fitted"]]
+    return res[cols]
 
 
 def run_holtwinters_forecast_gpu(demand_df: pd.DataFrame,
@@ -206,6 +295,8 @@ def run_fine_grained_forecast_sharded(
     horizon: int = FORECAST_HORIZON,
     orders=None,
     max_evals: int = 10,
+    forecast_steps: int = 0,
+    interval: Optional[float] = None,
 ) -> list:
     """W1 with restartable per-group-shard Parquet output.
 
@@ -220,9 +311,14 @@ def run_fine_grained_forecast_sharded(
     produces byte-identical output. Multi-worker: rank r owns shards
     r, r+world_size, ... (the reader-sharding convention).
 
+    ``forecast_steps`` / ``interval`` are passed to the engine (future
+    rows and interval columns in every shard).
+
     Returns the ordered list of shard paths.
     """
     import os
+
+    _check_forecast_args(forecast_steps, interval)
 
     os.makedirs(out_dir, exist_ok=True)
     if engine == "auto":
@@ -259,12 +355,17 @@ def run_fine_grained_forecast_sharded(
                 "Demand": pd.Series(dtype=float),
                 "Demand_Fitted": pd.Series(dtype=float),
             })
+            if interval is not None:
+                frame["Demand_Lower"] = pd.Series(dtype=float)
+                frame["Demand_Upper"] = pd.Series(dtype=float)
         elif engine == "gpu":
-            frame = run_fine_grained_forecast_gpu(part, orders=orders,
-                                                  horizon=horizon)
+            frame = run_fine_grained_forecast_gpu(
+                part, orders=orders, horizon=horizon,
+                forecast_steps=forecast_steps, interval=interval)
         else:
-            frame = run_fine_grained_forecast(part, max_evals=max_evals,
-                                              horizon=horizon)
+            frame = run_fine_grained_forecast(
+                part, max_evals=max_evals, horizon=horizon,
+                forecast_steps=forecast_steps, interval=interval)
         # deterministic row order -> byte-identical reruns
         frame = frame.sort_values(["Product", "SKU", "Date"]
                                   ).reset_index(drop=True)
@@ -290,11 +391,16 @@ def read_forecast_shards(out_dir: str) -> pd.DataFrame:
 def run_fine_grained_forecast(demand_df: pd.DataFrame,
                               num_workers: Optional[int] = None,
                               max_evals: int = 10,
-                              horizon: int = FORECAST_HORIZON
+                              horizon: int = FORECAST_HORIZON,
+                              forecast_steps: int = 0,
+                              interval: Optional[float] = None
                               ) -> pd.DataFrame:
     """The whole W1 job: enrich → group → tune+score per SKU (the
-    reference's :520-528 chain) on the local process pool."""
+    reference's :520-528 chain) on the local process pool.
+    ``forecast_steps`` / ``interval`` as in ``build_tune_and_score_model``.
+    """
     from ..groupby import LocalFrame
+    _check_forecast_args(forecast_steps, interval)
     if not set(EXO_COLS) <= set(demand_df.columns):
         demand_df = add_exo_variables(demand_df)
     n_groups = demand_df.groupby(["Product", "SKU"]).ngroups
@@ -303,5 +409,6 @@ def run_fine_grained_forecast(demand_df: pd.DataFrame,
                  .groupBy("Product", "SKU")
                  .applyInPandas(
                      lambda g: build_tune_and_score_model(
-                         g, horizon=horizon, max_evals=max_evals),
-                     TUNING_SCHEMA))
+                         g, horizon=horizon, max_evals=max_evals,
+                         forecast_steps=forecast_steps, interval=interval),
+                     _forecast_schema(interval)))

@@ -167,6 +167,40 @@ class SARIMAXResults:
             y2, y1 = y1, nxt
         return out
 
+    # -- forecast uncertainty (same definitions as the batched GPU path) ------
+    def psi_weights(self, steps: int) -> np.ndarray:
+        """psi_0..psi_{steps-1} of the fitted ARIMA(p,d,q): the MA(inf)
+        weights of ``theta(B) / (phi(B) (1-B)^d)``."""
+        ar = np.concatenate([[1.0], -self.phi])
+        for _ in range(self.order[1]):
+            ar = np.polymul(ar, [1.0, -1.0])
+        a = -ar[1:]
+        q = len(self.theta)
+        psi = np.zeros(steps)
+        for j in range(steps):
+            if j == 0:
+                psi[0] = 1.0
+                continue
+            acc = self.theta[j - 1] if j <= q else 0.0
+            for k in range(1, min(j, len(a)) + 1):
+                acc += a[k - 1] * psi[j - k]
+            psi[j] = acc
+        return psi
+
+    @property
+    def sigma2(self) -> float:
+        """Innovation variance: mean squared innovation past the first
+        max(p,q) steps of the differenced series."""
+        m = max(len(self.phi), len(self.theta))
+        e = self.eps[m:]
+        return float(np.sum(e * e) / len(e))
+
+    def forecast_se(self, steps: int) -> np.ndarray:
+        """Standard error of the ``steps``-ahead forecast in y-units,
+        regression coefficients treated as fixed (as statsmodels does)."""
+        psi = self.psi_weights(steps)
+        return np.sqrt(self.sigma2 * np.cumsum(psi * psi))
+
     def predict(self, start: int = 0, end: Optional[int] = None,
                 exog: Optional[np.ndarray] = None) -> np.ndarray:
         """statsmodels-style: in-sample one-step-ahead for t < T, dynamic

@@ -155,6 +155,68 @@ void groupfit_final(torch::Tensor yT, torch::Tensor xc0, torch::Tensor xc1,
       T, G, (int)xc0.size(1), stream.stream());
 }
 
+extern "C" void launch_groupfit_forecast(
+    const float* yT, const float* xc0, const float* xc1, const float* xc2,
+    const int* best_order, const float* params, float* forecast,
+    float* forecast_se, float* sigma2, unsigned char* statusv,
+    int T, long long G, int KX, int H, hipStream_t stream);
+
+// Forecast from stored coefficients. yT: [T][G]; xc{d}: [T+H-d][KX] stacked
+// designs (history rows, then H future rows); best_order: [G][3] i32;
+// params: [G][1+KX+8]; forecast, forecast_se: [H][G] out; sigma2: [G] out;
+// status: [G] u8 out. The kernel clamps orders to p,q <= 4, d <= 2, so
+// with T > 8 every lane has T - d - max(p,q) >= 3 residuals.
+void groupfit_forecast(torch::Tensor yT, torch::Tensor xc0,
+                       torch::Tensor xc1, torch::Tensor xc2,
+                       torch::Tensor best_order, torch::Tensor params,
+                       torch::Tensor forecast, torch::Tensor forecast_se,
+                       torch::Tensor sigma2, torch::Tensor status) {
+  _check_f32(yT, "yT"); _check_f32(params, "params");
+  _check_f32(forecast, "forecast"); _check_f32(forecast_se, "forecast_se");
+  _check_f32(sigma2, "sigma2");
+  TORCH_CHECK(yT.dim() == 2 && yT.size(1) >= 1, "yT must be [T][G>=1]");
+  const int64_t T = yT.size(0), G = yT.size(1);
+  TORCH_CHECK(T > 8 && T <= (1 << 24), "need 8 < T <= 2^24");
+  TORCH_CHECK(forecast.dim() == 2 && forecast.size(0) >= 1 &&
+                  forecast.size(1) == G,
+              "forecast must be [H>=1][G]");
+  const int64_t H = forecast.size(0);
+  TORCH_CHECK(H <= (1 << 24), "horizon too long");
+  TORCH_CHECK(forecast_se.dim() == 2 && forecast_se.size(0) == H &&
+                  forecast_se.size(1) == G,
+              "forecast_se must be [H][G]");
+  const torch::Tensor* xcs[3] = {&xc0, &xc1, &xc2};
+  const int64_t KX = xc0.dim() == 2 ? xc0.size(1) : -1;
+  TORCH_CHECK(KX >= 0 && KX <= 8, "xc0 must be 2-D with KX <= 8 columns");
+  for (int d = 0; d < 3; ++d) {
+    _check_f32(*xcs[d], "xc");
+    TORCH_CHECK(xcs[d]->dim() == 2 && xcs[d]->size(0) == T + H - d &&
+                    xcs[d]->size(1) == KX,
+                "xc", d, " must be [T+H-", d, "][KX]");
+  }
+  TORCH_CHECK(params.dim() == 2 && params.size(0) == G &&
+                  params.size(1) == 1 + KX + 8,
+              "params must be [G][1+KX+8]");
+  TORCH_CHECK(best_order.scalar_type() == torch::kInt32 &&
+                  best_order.is_cuda() && best_order.is_contiguous() &&
+                  best_order.dim() == 2 && best_order.size(0) == G &&
+                  best_order.size(1) == 3,
+              "best_order must be contiguous [G][3] i32 on GPU");
+  TORCH_CHECK(sigma2.numel() == G, "sigma2 must be [G]");
+  TORCH_CHECK(status.scalar_type() == torch::kUInt8 && status.is_cuda() &&
+                  status.is_contiguous() && status.numel() == G,
+              "status must be [G] u8 on GPU");
+  auto stream = at::cuda::getCurrentHIPStream();
+  launch_groupfit_forecast(
+      yT.data_ptr<float>(), xc0.data_ptr<float>(), xc1.data_ptr<float>(),
+      xc2.data_ptr<float>(), best_order.data_ptr<int>(),
+      params.data_ptr<float>(), forecast.data_ptr<float>(),
+      forecast_se.data_ptr<float>(), sigma2.data_ptr<float>(),
+      status.data_ptr<uint8_t>(), (int)T, (long long)G, (int)KX, (int)H,
+      stream.stream());
+  C10_HIP_KERNEL_LAUNCH_CHECK();
+}
+
 extern "C" int launch_hwfit_search(const float* yT, const float* table,
                                    float* params, float* sse,
                                    unsigned char* statusv, int T,
@@ -949,6 +1011,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "batched per-group ARIMAX candidate evaluation (validation MSE)");
   m.def("groupfit_final", &groupfit_final,
         "batched per-group final fit (fitted values + params)");
+  m.def("groupfit_forecast", &groupfit_forecast,
+        "batched per-group forecast from stored coefficients (forecast, "
+        "standard error, sigma2)");
   m.def("hwfit_search", &hwfit_search,
         "batched Holt-Winters grid + refinement search (params, sse)",
         pybind11::arg("yT"), pybind11::arg("table"), pybind11::arg("params"),

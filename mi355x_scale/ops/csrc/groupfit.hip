@@ -525,6 +525,166 @@ extern "C" __global__ __launch_bounds__(WAVE) void groupfit_final_kernel(
   }
 }
 
+// Out-of-sample forecast from STORED coefficients: no fitting and no LDS
+// state block. wm, beta, phi, theta come from `params` into registers; one
+// streaming pass over t rebuilds the end-of-series u/e rings (the
+// fitted-value recursion of the final kernel) and accumulates
+//   sigma2 = 1/(n-m) sum_{td>=m} e_td^2,   m = max(p,q);
+// then H steps of the forecast recursion, integrated to y-units, next to
+// the psi-weight recursion of the ARIMA(p,d,q) process
+//   1 - sum a_k B^k = (1 - sum phi_i B^i)(1-B)^d        (p + d <= 6)
+//   psi_0 = 1,  psi_j = theta_j [j<=q] + sum_k a_k psi_{j-k}
+//   se_h  = sqrt(sigma2 * sum_{j<=h} psi_j^2).
+// xc{d} are the STACKED designs: T-d history rows, then H future rows.
+// Orders are per lane; they are clamped to p,q <= 4, d <= 2, so a lane
+// always has n - m >= T - 6 residuals and reads inside xc{d}.
+extern "C" __global__ __launch_bounds__(WAVE) void groupfit_forecast_kernel(
+    const float* __restrict__ yT,
+    const float* __restrict__ xc0, const float* __restrict__ xc1,
+    const float* __restrict__ xc2,        // [T+H-d][KX]
+    const int* __restrict__ best_order,   // [G][3]
+    const float* __restrict__ params,     // [G][1+KX+8]
+    float* __restrict__ forecast,         // [H][G]
+    float* __restrict__ forecast_se,      // [H][G]
+    float* __restrict__ sigma2v,          // [G]
+    unsigned char* __restrict__ statusv,  // [G]
+    int T, long long G, int KX, int H) {
+  const int lane = threadIdx.x;
+  const long long g = (long long)blockIdx.x * WAVE + lane;
+  const bool active = g < G;
+  const long long gg = active ? g : (G - 1);
+  const int p = min(max(best_order[gg * 3 + 0], 0), 4);
+  const int d = min(max(best_order[gg * 3 + 1], 0), 2);
+  const int q = min(max(best_order[gg * 3 + 2], 0), 4);
+  const float* xc = (d == 0) ? xc0 : (d == 1) ? xc1 : xc2;
+  const int n = T - d;
+  const int m = max(p, q);
+
+  const float* pp = params + gg * (1 + KX + 8);
+  const float wm = pp[0];
+  float beta[MAXK], ph[4], th[4];
+#pragma unroll
+  for (int k = 0; k < MAXK; ++k) beta[k] = (k < KX) ? pp[1 + k] : 0.0f;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    ph[i] = pp[1 + KX + i];
+    th[i] = pp[1 + KX + 4 + i];
+  }
+
+  // ---- streaming pass: end-of-series rings + residual sum of squares.
+  // The y load of step t+1 is issued before the recursion of step t.
+  float ur[8], er[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) { ur[j] = 0.0f; er[j] = 0.0f; }
+  float y0 = 0.0f, y1 = 0.0f, sse = 0.0f;
+  float ynext = yT[gg];
+  for (int t = 0; t < T; ++t) {
+    const float yv = ynext;
+    if (t + 1 < T) ynext = yT[(long long)(t + 1) * G + gg];
+    float w;
+    if (d == 0) w = yv;
+    else if (d == 1) w = yv - y0;
+    else w = yv - 2.0f * y0 + y1;
+    y1 = y0; y0 = yv;
+    if (t >= d) {
+      const int td = t - d;
+      float regx = 0.0f;
+#pragma unroll
+      for (int k = 0; k < MAXK; ++k)
+        if (k < KX) regx += xc[(long long)td * KX + k] * beta[k];
+      const float acc = ph[0] * ur[0] + ph[1] * ur[1] + ph[2] * ur[2] +
+                        ph[3] * ur[3] + th[0] * er[0] + th[1] * er[1] +
+                        th[2] * er[2] + th[3] * er[3];
+      const float u = (w - wm) - regx;
+      const float e = u - acc;
+      if (td >= m) sse += e * e;
+      RING_SHIFT(ur, u);
+      RING_SHIFT(er, e);
+    }
+  }
+  const float sigma2 = sse / (float)(n - m);
+
+  // ---- a_k = -c_k, c = (1 - sum phi_i B^i)(1-B)^d, by polynomial product
+  float c[7];
+  c[0] = 1.0f;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) c[1 + i] = -ph[i];
+  c[5] = 0.0f; c[6] = 0.0f;
+#pragma unroll
+  for (int r = 0; r < 2; ++r) {
+    if (r < d) {
+#pragma unroll
+      for (int k = 6; k > 0; --k) c[k] = c[k] - c[k - 1];
+    }
+  }
+
+  // ---- H steps: forecast recursion + psi recursion. pr[j] = psi_{h-1-j};
+  // tq is theta shifted so that tq[0] is the theta term of the next psi.
+  float pr[8], tq[4];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) pr[j] = 0.0f;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) tq[i] = th[i];
+  float psi = 1.0f, cum = 0.0f;
+  const float ylast = y0;        // y_{T-1}
+  float yl1 = y0, yl2 = y1;      // y_{T-1}, y_{T-2}
+  float wsum = 0.0f;
+  bool fin = isfinite(sigma2);
+  for (int h = 0; h < H; ++h) {
+    float regx = 0.0f;
+#pragma unroll
+    for (int k = 0; k < MAXK; ++k)
+      if (k < KX) regx += xc[(long long)(n + h) * KX + k] * beta[k];
+    const float acc = ph[0] * ur[0] + ph[1] * ur[1] + ph[2] * ur[2] +
+                      ph[3] * ur[3] + th[0] * er[0] + th[1] * er[1] +
+                      th[2] * er[2] + th[3] * er[3];
+    const float w_pred = wm + regx + acc;
+    RING_SHIFT(ur, acc);         // future u = ARMA part, future e = 0
+    RING_SHIFT(er, 0.0f);
+    // d = 1 sums the small w_pred first and adds y_{T-1} once, as the
+    // oracle does: one rounding at the size of y, not one per step
+    float y_pred;
+    if (d == 0) {
+      y_pred = w_pred;
+    } else if (d == 1) {
+      wsum += w_pred;
+      y_pred = ylast + wsum;
+    } else {
+      y_pred = w_pred + 2.0f * yl1 - yl2;
+      yl2 = yl1; yl1 = y_pred;
+    }
+
+    cum += psi * psi;            // psi = psi_h here
+    const float se = sqrtf(sigma2 * cum);
+    RING_SHIFT(pr, psi);
+    psi = tq[0];
+#pragma unroll
+    for (int k = 0; k < 6; ++k) psi -= c[1 + k] * pr[k];
+    tq[0] = tq[1]; tq[1] = tq[2]; tq[2] = tq[3]; tq[3] = 0.0f;
+
+    fin = fin && isfinite(y_pred) && isfinite(se);
+    if (active) {
+      forecast[(long long)h * G + g] = y_pred;
+      forecast_se[(long long)h * G + g] = se;
+    }
+  }
+  if (active) {
+    sigma2v[g] = sigma2;
+    statusv[g] = fin ? 1 : 0;
+  }
+}
+
+extern "C" void launch_groupfit_forecast(
+    const float* yT, const float* xc0, const float* xc1, const float* xc2,
+    const int* best_order, const float* params, float* forecast,
+    float* forecast_se, float* sigma2, unsigned char* statusv,
+    int T, long long G, int KX, int H, hipStream_t stream) {
+  const int blocks = (int)((G + WAVE - 1) / WAVE);
+  hipLaunchKernelGGL(groupfit_forecast_kernel, dim3(blocks), dim3(WAVE), 0,
+                     stream, yT, xc0, xc1, xc2, best_order, params, forecast,
+                     forecast_se, sigma2, statusv, T, G, KX, H);
+}
+
 extern "C" void launch_groupfit_eval(
     const float* yT, const float* xc0, const float* xc1, const float* xc2,
     const float* pj0, const float* pj1, const float* pj2, const int* orders,

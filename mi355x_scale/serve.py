@@ -13,7 +13,9 @@ Endpoints:
                                   normalize + bf16 path as training
   POST /forecast               -> per-group demand forecast: long-format
                                   records in, fitted values out (the W1
-                                  GPU pipeline under the hood)
+                                  GPU pipeline under the hood); with
+                                  forecast_steps > 0 future rows follow,
+                                  with interval their lower/upper bounds
 """
 from typing import Optional
 
@@ -34,6 +36,8 @@ class ClassifyRequest(BaseModel):
 class ForecastRequest(BaseModel):
     records: list  # [{Product, SKU, Date, Demand}]
     horizon: int = 40
+    forecast_steps: int = 0           # future rows per group
+    interval: Optional[float] = None  # e.g. 0.9 -> Demand_Lower/_Upper
 
 
 def create_app(classifier=None, model_name: str = "resnet18",
@@ -81,17 +85,29 @@ def create_app(classifier=None, model_name: str = "resnet18",
         need = {"Product", "SKU", "Date", "Demand"}
         if not need <= set(df.columns):
             raise HTTPException(400, f"records need columns {sorted(need)}")
+        if req.forecast_steps < 0:
+            raise HTTPException(400, "forecast_steps must be >= 0")
+        if req.interval is not None and not 0.0 < req.interval < 1.0:
+            raise HTTPException(400, "interval must be in (0, 1)")
+        kw = dict(horizon=req.horizon, forecast_steps=req.forecast_steps,
+                  interval=req.interval)
         if dev.type == "cuda":
             from .forecast.pipeline import run_fine_grained_forecast_gpu
-            out = run_fine_grained_forecast_gpu(df, horizon=req.horizon)
+            out = run_fine_grained_forecast_gpu(df, **kw)
         else:
             from .forecast.pipeline import run_fine_grained_forecast
-            out = run_fine_grained_forecast(df, horizon=req.horizon,
-                                            max_evals=5)
+            out = run_fine_grained_forecast(df, max_evals=5, **kw)
         out = out.copy()
         out["Date"] = out["Date"].astype(str)
         for c in ("Product", "SKU"):
             out[c] = out[c].astype(str)
-        return {"rows": out.to_dict(orient="records")}
+        rows = out.to_dict(orient="records")
+        if req.forecast_steps > 0 or req.interval is not None:
+            # NaN (future Demand, interval on history rows) is not JSON
+            for row in rows:
+                for k, v in row.items():
+                    if isinstance(v, float) and v != v:
+                        row[k] = None
+        return {"rows": rows}
 
     return app
