@@ -5,9 +5,9 @@ forecast and standard errors, against the same job without it.
 
     python benchmarks/bench_groupfit_forecast.py
 
-The two variants are timed in alternating runs. ``groupfit_forecast`` and
-``groupfit_final`` are also timed alone by device events, on the same
-panel, orders and coefficients. The GPU work runs in a child process under
+The two variants are timed in alternating runs. ``groupfit_eval``,
+``groupfit_final`` and ``groupfit_forecast`` are also timed alone by device
+events, on the same panel, orders and coefficients. The GPU work runs in a child process under
 its own time limit, and nothing more is started after it fails. One JSON
 line is printed.
 """
@@ -44,6 +44,7 @@ def worker(groups: int, weeks: int, train_len: int, repeats: int) -> dict:
     from mi355x_scale.forecast.batched import (_designs_to_gpu,
                                                _mfma_projection, _to_yT,
                                                batched_fit_gpu,
+                                               make_exog_designs,
                                                stacked_exog_designs)
     from mi355x_scale.forecast.pipeline import DEFAULT_GPU_ORDERS
     from mi355x_scale.ops import _C, require_ext
@@ -65,8 +66,16 @@ def worker(groups: int, weeks: int, train_len: int, repeats: int) -> dict:
             times[name].append(time.perf_counter() - t0)
     ok = float(out["forecast_status"].float().mean().item())
 
-    # the two kernels alone, by device events, on the job's own buffers
+    # the three kernels alone, by device events, on the job's own buffers
     yT = _to_yT(y, "cuda")
+    xs_e, ps_e = _designs_to_gpu(make_exog_designs(exog, train_len), "cuda")
+    betas_e, wms_e = _mfma_projection(yT, ps_e, train_len, "cuda")
+    orders_t = torch.tensor(list(orders), dtype=torch.int32,
+                            device="cuda").reshape(-1, 3)
+    mse = torch.empty((len(orders_t), groups), dtype=torch.float32,
+                      device="cuda")
+    est = torch.empty((len(orders_t), groups), dtype=torch.uint8,
+                      device="cuda")
     xs, ps = _designs_to_gpu(stacked_exog_designs(exog, fx, weeks), "cuda")
     betas, wms = _mfma_projection(yT, ps, weeks, "cuda")
     best, params = out["best_order"], out["params"]
@@ -79,6 +88,12 @@ def worker(groups: int, weeks: int, train_len: int, repeats: int) -> dict:
     s2 = torch.empty((groups,), dtype=torch.float32, device="cuda")
     st = torch.empty((groups,), dtype=torch.uint8, device="cuda")
 
+    def run_eval():
+        _C.groupfit_eval(yT, xs_e[0], xs_e[1], xs_e[2], ps_e[0], ps_e[1],
+                         ps_e[2], orders_t, mse, est, train_len,
+                         betas_e[0], betas_e[1], betas_e[2],
+                         wms_e[0], wms_e[1], wms_e[2])
+
     def run_final():
         _C.groupfit_final(yT, xs[0], xs[1], xs[2], ps[0], ps[1], ps[2],
                           best, fitted, par2, fstatus,
@@ -90,7 +105,8 @@ def worker(groups: int, weeks: int, train_len: int, repeats: int) -> dict:
                              fc, se, s2, st)
 
     kernel_ms = {}
-    for name, fn in (("groupfit_final", run_final),
+    for name, fn in (("groupfit_eval", run_eval),
+                     ("groupfit_final", run_final),
                      ("groupfit_forecast", run_forecast)):
         fn()
         torch.cuda.synchronize()

@@ -23,8 +23,9 @@ Yule-Walker/Levinson for the long-AR stage):
 
 ``batched_fit_reference`` is the vectorized-f64 numpy implementation —
 the numerics oracle for the HIP kernel (``ops/csrc/groupfit.hip``), which
-runs one group per lane, 64 groups per wave, series slabs in LDS,
-time-major [T, G] global layout for coalescing.
+runs one group per lane, 64 groups per wave, over a time-major [T, G]
+global layout for coalescing; it streams the series and keeps only small
+per-lane matrices in LDS.
 
 Out-of-sample: ``forecast_from_params_reference`` /
 ``batched_forecast_reference`` define the H-step forecast, the innovation
@@ -260,6 +261,27 @@ def _to_yT(y, device):
     return y_t.t().contiguous().to(device)
 
 
+def _check_orders(orders) -> None:
+    """Every order is an integer (p, d, q) within what the kernels hold:
+    ``p <= MAXP``, ``q <= MAXQ``, ``d <= MAXD``, none negative."""
+    for o in orders:
+        try:
+            p, d, q = o
+            ok = all(int(v) == v for v in o)
+        except (TypeError, ValueError):
+            ok = False
+        if not (ok and 0 <= p <= MAXP and 0 <= d <= MAXD and 0 <= q <= MAXQ):
+            raise ValueError(
+                f"order {o!r} is not an integer (p, d, q) with 0 <= p <= "
+                f"{MAXP}, 0 <= d <= {MAXD}, 0 <= q <= {MAXQ}")
+
+
+def _orders_to_gpu(orders, device):
+    import torch
+    return torch.tensor(orders, dtype=torch.int32,
+                        device=device).reshape(-1, 3)
+
+
 def _mfma_projection(yT, ps, train_len: int, device):
     """Stage-1 via the MFMA design-matrix GEMM for each d: Wc/wm from the
     diff+center kernel, beta = P_d @ Wc on the f32 matrix cores."""
@@ -280,10 +302,26 @@ def _mfma_projection(yT, ps, train_len: int, device):
     return betas, wms
 
 
+def _stage1(yT, ps, train_len: int, device, use_mfma: bool):
+    """``(betas, wms)`` for the fit kernels: from the MFMA projection, or
+    empty tensors, which make the kernels run stage 1 themselves."""
+    if use_mfma:
+        return _mfma_projection(yT, ps, train_len, device)
+    import torch
+    empty = torch.empty(0, dtype=torch.float32, device=device)
+    return [empty] * 3, [empty] * 3
+
+
 def batched_eval_gpu(y, exog, orders, train_len: int, device="cuda",
-                     yT=None, use_mfma: bool = True):
+                     yT=None, use_mfma: bool = True, orders_t=None):
     """GPU candidate evaluation: returns (mse [G,C] torch.f32, status
-    [G,C] torch.u8). ``y`` is [G,T] (numpy or torch)."""
+    [G,C] torch.u8). ``y`` is [G,T] (numpy or torch); ``orders_t`` is
+    ``orders`` as a [C,3] i32 device tensor when the caller has it."""
+    orders = list(orders)
+    _check_orders(orders)
+    T = np.shape(y)[1] if yT is None else yT.shape[0]
+    if not 8 < train_len < T:
+        raise ValueError(f"need 8 < train_len < T = {T}, got {train_len}")
     import torch
     from ..ops import require_ext, _C
     require_ext()
@@ -292,13 +330,9 @@ def batched_eval_gpu(y, exog, orders, train_len: int, device="cuda",
     T, G = yT.shape
     designs = make_exog_designs(exog, train_len)
     xs, ps = _designs_to_gpu(designs, device)
-    if use_mfma:
-        betas, wms = _mfma_projection(yT, ps, train_len, device)
-    else:
-        empty = torch.empty(0, dtype=torch.float32, device=device)
-        betas, wms = [empty] * 3, [empty] * 3
-    orders_t = torch.tensor(list(orders), dtype=torch.int32,
-                            device=device).reshape(-1, 3).contiguous()
+    betas, wms = _stage1(yT, ps, train_len, device, use_mfma)
+    if orders_t is None:
+        orders_t = _orders_to_gpu(orders, device)
     C = orders_t.shape[0]
     mse = torch.empty((C, G), dtype=torch.float32, device=device)
     status = torch.empty((C, G), dtype=torch.uint8, device=device)
@@ -363,6 +397,8 @@ def batched_forecast_gpu(y, exog, future_exog, best_order, params,
         raise ValueError(f"best_order must be [{G}, 3], got shape "
                          f"{tuple(np.shape(best_order))}")
     import torch
+    if not isinstance(best_order, torch.Tensor) or not best_order.is_cuda:
+        _check_orders(np.asarray(best_order).tolist())
     from ..ops import require_ext
     require_ext()
     yT = _to_yT(y, device)
@@ -386,15 +422,17 @@ def batched_fit_gpu(y, exog, orders, train_len: int, device="cuda",
     [G] and ``forecast_status`` [G] are added, the other keys unchanged."""
     import torch
     from ..ops import require_ext, _C
+    orders = list(orders)
+    _check_orders(orders)
     if future_exog is not None:
         H = _check_future_exog(exog, future_exog, np.shape(y)[1])
     require_ext()
     yT = _to_yT(y, device)
     T, G = yT.shape
+    orders_t = _orders_to_gpu(orders, device)
     mse, status = batched_eval_gpu(y, exog, orders, train_len, device,
-                                   yT=yT, use_mfma=use_mfma)
-    orders_t = torch.tensor(list(orders), dtype=torch.int32, device=device
-                            ).reshape(-1, 3)
+                                   yT=yT, use_mfma=use_mfma,
+                                   orders_t=orders_t)
     best_ci = mse.argmin(dim=1)                        # [G]
     best_order = orders_t[best_ci].contiguous()        # [G,3]
     if future_exog is None:
@@ -404,13 +442,8 @@ def batched_fit_gpu(y, exog, orders, train_len: int, device="cuda",
         designs = stacked_exog_designs(exog, future_exog, T)
     xs, ps = _designs_to_gpu(designs, device)
     KX = xs[0].shape[1]
-    if use_mfma:
-        # stage 1 for the final fit on the matrix cores too (full-series
-        # design, train_len = T)
-        betas, wms = _mfma_projection(yT, ps, T, device)
-    else:
-        empty = torch.empty(0, dtype=torch.float32, device=device)
-        betas, wms = [empty] * 3, [empty] * 3
+    # stage 1 of the final fit over the full-series design (train_len = T)
+    betas, wms = _stage1(yT, ps, T, device, use_mfma)
     fitted = torch.empty((T, G), dtype=torch.float32, device=device)
     params = torch.empty((G, 1 + KX + 8), dtype=torch.float32,
                          device=device)

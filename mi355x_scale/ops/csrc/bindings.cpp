@@ -8,6 +8,8 @@
 #include <cstdint>
 #include <cstdlib>
 
+#include "groupfit.h"   // launch operands of the group-fit kernels
+
 extern "C" void launch_normalize_u8_to_bf16(
     const uint8_t* in, void* out, const float* scale_dev,
     const float* shift_dev, long long n, hipStream_t stream);
@@ -37,15 +39,6 @@ void normalize_u8_to_bf16(torch::Tensor in, torch::Tensor out,
       (long long)in.numel(), stream.stream());
 }
 
-extern "C" void launch_groupfit_eval(
-    const float* yT, const float* xc0, const float* xc1, const float* xc2,
-    const float* pj0, const float* pj1, const float* pj2, const int* orders,
-    float* mse, unsigned char* statusv,
-    const float* b0, const float* b1, const float* b2,
-    const float* w0, const float* w1, const float* w2,
-    int T, long long G, int S, int C,
-    int KX, hipStream_t stream);
-
 extern "C" void launch_diff_center(const float* yT, float* wc, float* wm,
                                    int T, long long G, int S, int d,
                                    hipStream_t stream);
@@ -53,15 +46,6 @@ extern "C" void launch_diff_center(const float* yT, float* wc, float* wm,
 extern "C" void launch_exog_project_mfma(const float* P, const float* wc,
                                          float* beta, int n, long long G,
                                          int KX, hipStream_t stream);
-
-extern "C" void launch_groupfit_final(
-    const float* yT, const float* xc0, const float* xc1, const float* xc2,
-    const float* pj0, const float* pj1, const float* pj2,
-    const int* best_order, float* fitted, float* params,
-    unsigned char* statusv,
-    const float* b0, const float* b1, const float* b2,
-    const float* w0, const float* w1, const float* w2,
-    int T, long long G, int KX, hipStream_t stream);
 
 extern "C" void launch_stem_conv_fwd(const void* x, const void* w, void* out,
                                      void* wp_scratch, float* partial,
@@ -99,36 +83,96 @@ static void _check_code(const torch::Tensor& code) {
               "code must be contiguous u8 on GPU");
 }
 
-// yT: [T][G] time-major; xc{d}: [T-d][KX]; pj{d}: [KX][S-d];
-// orders: [C][3] i32; mse: [C][G] f32 out; status: [C][G] u8 out
+// A GPU tensor of the given dtype and exact shape, contiguous.
+static void _check_shape(const torch::Tensor& t, torch::ScalarType dtype,
+                         at::IntArrayRef shape, const char* name) {
+  TORCH_CHECK(t.is_cuda() && t.scalar_type() == dtype && t.is_contiguous() &&
+                  t.sizes() == shape,
+              name, " must be a contiguous ", dtype, " GPU tensor of shape ",
+              shape, ", got ", t.scalar_type(), " ", t.sizes());
+}
+
+// ------------------------------------------------------------ group fit
+// What the three group-fit entry points share. yT: [T][G] time-major;
+// xc{d}: centered exog design of differencing order d, [rows-d][KX];
+// orders: [C][3] or [G][3] i32 (p, d, q).
+struct _GroupfitGeom { int64_t T, G, KX; };
+
+// The designs must cover T + extra_rows y-rows: exactly (the forecast reads
+// T+H of them) or at least (a fit reads T, and is also given the stacked
+// designs of a forecast to follow).
+static _GroupfitGeom _check_groupfit_panel(
+    const torch::Tensor& yT, const torch::Tensor& xc0,
+    const torch::Tensor& xc1, const torch::Tensor& xc2, int64_t extra_rows,
+    bool exact) {
+  _check_f32(yT, "yT");
+  TORCH_CHECK(yT.dim() == 2 && yT.size(1) >= 1, "yT must be [T][G>=1]");
+  const _GroupfitGeom g{yT.size(0), yT.size(1),
+                        xc0.dim() == 2 ? xc0.size(1) : -1};
+  TORCH_CHECK(g.T > 8 && g.T <= (1 << 24), "need 8 < T <= 2^24");
+  TORCH_CHECK(g.KX >= 0 && g.KX <= 8,
+              "xc0 must be 2-D with KX <= 8 columns");
+  const torch::Tensor* xcs[3] = {&xc0, &xc1, &xc2};
+  for (int d = 0; d < 3; ++d) {
+    const int64_t rows = g.T + extra_rows - d;
+    _check_f32(*xcs[d], "xc");
+    TORCH_CHECK(xcs[d]->dim() == 2 && xcs[d]->size(1) == g.KX &&
+                    (exact ? xcs[d]->size(0) == rows
+                           : xcs[d]->size(0) >= rows),
+                "xc", d, " must be [", rows, exact ? "" : " or more",
+                "][KX]");
+  }
+  return g;
+}
+
+// Stage-1 operands of a fit on S rows: pj{d} [KX][S-d]; b{d} / w{d} empty
+// ("compute in the kernel") or [KX][G] / [G].
+static void _check_groupfit_stage1(const _GroupfitGeom& g, int64_t S,
+                                   const torch::Tensor* const pj[3],
+                                   const torch::Tensor* const b[3],
+                                   const torch::Tensor* const w[3]) {
+  for (int d = 0; d < 3; ++d) {
+    _check_shape(*pj[d], torch::kFloat32, {g.KX, S - d}, "pj{d}");
+    if (b[d]->numel())
+      _check_shape(*b[d], torch::kFloat32, {g.KX, g.G}, "b{d}");
+    if (w[d]->numel())
+      _check_shape(*w[d], torch::kFloat32, {g.G}, "w{d}");
+  }
+}
+
+// Candidate evaluation on the first S rows, scored on the rest.
+// pj{d}: [KX][S-d]; orders: [C][3] i32; mse: [C][G] f32 out; status:
+// [C][G] u8 out; b{d}, w{d}: stage 1 of the MFMA projection, or empty.
 void groupfit_eval(torch::Tensor yT, torch::Tensor xc0, torch::Tensor xc1,
                    torch::Tensor xc2, torch::Tensor pj0, torch::Tensor pj1,
                    torch::Tensor pj2, torch::Tensor orders,
                    torch::Tensor mse, torch::Tensor status, int64_t S,
                    torch::Tensor b0, torch::Tensor b1, torch::Tensor b2,
                    torch::Tensor w0, torch::Tensor w1, torch::Tensor w2) {
-  _check_f32(yT, "yT"); _check_f32(xc0, "xc0"); _check_f32(xc1, "xc1");
-  _check_f32(xc2, "xc2"); _check_f32(pj0, "pj0"); _check_f32(pj1, "pj1");
-  _check_f32(pj2, "pj2"); _check_f32(mse, "mse");
-  TORCH_CHECK(orders.scalar_type() == torch::kInt32 && orders.is_cuda());
-  TORCH_CHECK(status.scalar_type() == torch::kUInt8 && status.is_cuda());
-  int T = yT.size(0);
-  long long G = yT.size(1);
-  int C = orders.size(0);
-  TORCH_CHECK(S > 8 && S <= T, "need 8 < S <= T");
-  TORCH_CHECK(mse.size(0) == C && mse.size(1) == G);
-  auto stream = at::cuda::getCurrentHIPStream();
-  launch_groupfit_eval(
+  const _GroupfitGeom g = _check_groupfit_panel(yT, xc0, xc1, xc2, 0, false);
+  TORCH_CHECK(S > 8 && S <= g.T, "need 8 < S <= T");
+  const torch::Tensor *pj[3] = {&pj0, &pj1, &pj2}, *b[3] = {&b0, &b1, &b2},
+                      *w[3] = {&w0, &w1, &w2};
+  _check_groupfit_stage1(g, S, pj, b, w);
+  TORCH_CHECK(orders.dim() == 2, "orders must be [C][3]");
+  const int64_t C = orders.size(0);
+  _check_shape(orders, torch::kInt32, {C, 3}, "orders");
+  _check_shape(mse, torch::kFloat32, {C, g.G}, "mse");
+  _check_shape(status, torch::kUInt8, {C, g.G}, "status");
+  const GroupfitEvalArgs a{
       yT.data_ptr<float>(), xc0.data_ptr<float>(), xc1.data_ptr<float>(),
       xc2.data_ptr<float>(), pj0.data_ptr<float>(), pj1.data_ptr<float>(),
       pj2.data_ptr<float>(), orders.data_ptr<int>(), mse.data_ptr<float>(),
       status.data_ptr<uint8_t>(),
       _f32_or_null(b0), _f32_or_null(b1), _f32_or_null(b2),
       _f32_or_null(w0), _f32_or_null(w1), _f32_or_null(w2),
-      T, G, (int)S, C, (int)xc0.size(1),
-      stream.stream());
+      (int)g.T, (long long)g.G, (int)S, (int)C, (int)g.KX};
+  launch_groupfit_eval(a, at::cuda::getCurrentHIPStream().stream());
+  C10_HIP_KERNEL_LAUNCH_CHECK();
 }
 
+// Final fit on the whole series (S = T). best_order: [G][3] i32; fitted:
+// [T][G] out; params: [G][1+KX+8] out; status: [G] u8 out.
 void groupfit_final(torch::Tensor yT, torch::Tensor xc0, torch::Tensor xc1,
                     torch::Tensor xc2, torch::Tensor pj0, torch::Tensor pj1,
                     torch::Tensor pj2, torch::Tensor best_order,
@@ -136,15 +180,15 @@ void groupfit_final(torch::Tensor yT, torch::Tensor xc0, torch::Tensor xc1,
                     torch::Tensor status,
                     torch::Tensor b0, torch::Tensor b1, torch::Tensor b2,
                     torch::Tensor w0, torch::Tensor w1, torch::Tensor w2) {
-  _check_f32(yT, "yT"); _check_f32(fitted, "fitted");
-  _check_f32(params, "params");
-  TORCH_CHECK(best_order.scalar_type() == torch::kInt32 &&
-              best_order.is_cuda());
-  int T = yT.size(0);
-  long long G = yT.size(1);
-  TORCH_CHECK(fitted.size(0) == T && fitted.size(1) == G);
-  auto stream = at::cuda::getCurrentHIPStream();
-  launch_groupfit_final(
+  const _GroupfitGeom g = _check_groupfit_panel(yT, xc0, xc1, xc2, 0, false);
+  const torch::Tensor *pj[3] = {&pj0, &pj1, &pj2}, *b[3] = {&b0, &b1, &b2},
+                      *w[3] = {&w0, &w1, &w2};
+  _check_groupfit_stage1(g, g.T, pj, b, w);
+  _check_shape(best_order, torch::kInt32, {g.G, 3}, "best_order");
+  _check_shape(fitted, torch::kFloat32, {g.T, g.G}, "fitted");
+  _check_shape(params, torch::kFloat32, {g.G, 1 + g.KX + 8}, "params");
+  _check_shape(status, torch::kUInt8, {g.G}, "status");
+  const GroupfitFinalArgs a{
       yT.data_ptr<float>(), xc0.data_ptr<float>(), xc1.data_ptr<float>(),
       xc2.data_ptr<float>(), pj0.data_ptr<float>(), pj1.data_ptr<float>(),
       pj2.data_ptr<float>(), best_order.data_ptr<int>(),
@@ -152,18 +196,14 @@ void groupfit_final(torch::Tensor yT, torch::Tensor xc0, torch::Tensor xc1,
       status.data_ptr<uint8_t>(),
       _f32_or_null(b0), _f32_or_null(b1), _f32_or_null(b2),
       _f32_or_null(w0), _f32_or_null(w1), _f32_or_null(w2),
-      T, G, (int)xc0.size(1), stream.stream());
+      (int)g.T, (long long)g.G, (int)g.KX};
+  launch_groupfit_final(a, at::cuda::getCurrentHIPStream().stream());
+  C10_HIP_KERNEL_LAUNCH_CHECK();
 }
 
-extern "C" void launch_groupfit_forecast(
-    const float* yT, const float* xc0, const float* xc1, const float* xc2,
-    const int* best_order, const float* params, float* forecast,
-    float* forecast_se, float* sigma2, unsigned char* statusv,
-    int T, long long G, int KX, int H, hipStream_t stream);
-
-// Forecast from stored coefficients. yT: [T][G]; xc{d}: [T+H-d][KX] stacked
-// designs (history rows, then H future rows); best_order: [G][3] i32;
-// params: [G][1+KX+8]; forecast, forecast_se: [H][G] out; sigma2: [G] out;
+// Forecast from stored coefficients. xc{d}: [T+H-d][KX] stacked designs
+// (history rows, then H future rows); best_order: [G][3] i32; params:
+// [G][1+KX+8]; forecast, forecast_se: [H][G] out; sigma2: [G] out;
 // status: [G] u8 out. The kernel clamps orders to p,q <= 4, d <= 2, so
 // with T > 8 every lane has T - d - max(p,q) >= 3 residuals.
 void groupfit_forecast(torch::Tensor yT, torch::Tensor xc0,
@@ -171,49 +211,26 @@ void groupfit_forecast(torch::Tensor yT, torch::Tensor xc0,
                        torch::Tensor best_order, torch::Tensor params,
                        torch::Tensor forecast, torch::Tensor forecast_se,
                        torch::Tensor sigma2, torch::Tensor status) {
-  _check_f32(yT, "yT"); _check_f32(params, "params");
-  _check_f32(forecast, "forecast"); _check_f32(forecast_se, "forecast_se");
-  _check_f32(sigma2, "sigma2");
-  TORCH_CHECK(yT.dim() == 2 && yT.size(1) >= 1, "yT must be [T][G>=1]");
-  const int64_t T = yT.size(0), G = yT.size(1);
-  TORCH_CHECK(T > 8 && T <= (1 << 24), "need 8 < T <= 2^24");
   TORCH_CHECK(forecast.dim() == 2 && forecast.size(0) >= 1 &&
-                  forecast.size(1) == G,
-              "forecast must be [H>=1][G]");
+                  forecast.size(0) <= (1 << 24),
+              "forecast must be [1 <= H <= 2^24][G]");
   const int64_t H = forecast.size(0);
-  TORCH_CHECK(H <= (1 << 24), "horizon too long");
-  TORCH_CHECK(forecast_se.dim() == 2 && forecast_se.size(0) == H &&
-                  forecast_se.size(1) == G,
-              "forecast_se must be [H][G]");
-  const torch::Tensor* xcs[3] = {&xc0, &xc1, &xc2};
-  const int64_t KX = xc0.dim() == 2 ? xc0.size(1) : -1;
-  TORCH_CHECK(KX >= 0 && KX <= 8, "xc0 must be 2-D with KX <= 8 columns");
-  for (int d = 0; d < 3; ++d) {
-    _check_f32(*xcs[d], "xc");
-    TORCH_CHECK(xcs[d]->dim() == 2 && xcs[d]->size(0) == T + H - d &&
-                    xcs[d]->size(1) == KX,
-                "xc", d, " must be [T+H-", d, "][KX]");
-  }
-  TORCH_CHECK(params.dim() == 2 && params.size(0) == G &&
-                  params.size(1) == 1 + KX + 8,
-              "params must be [G][1+KX+8]");
-  TORCH_CHECK(best_order.scalar_type() == torch::kInt32 &&
-                  best_order.is_cuda() && best_order.is_contiguous() &&
-                  best_order.dim() == 2 && best_order.size(0) == G &&
-                  best_order.size(1) == 3,
-              "best_order must be contiguous [G][3] i32 on GPU");
-  TORCH_CHECK(sigma2.numel() == G, "sigma2 must be [G]");
-  TORCH_CHECK(status.scalar_type() == torch::kUInt8 && status.is_cuda() &&
-                  status.is_contiguous() && status.numel() == G,
-              "status must be [G] u8 on GPU");
-  auto stream = at::cuda::getCurrentHIPStream();
-  launch_groupfit_forecast(
+  const _GroupfitGeom g = _check_groupfit_panel(yT, xc0, xc1, xc2, H, true);
+  _check_shape(best_order, torch::kInt32, {g.G, 3}, "best_order");
+  _check_shape(params, torch::kFloat32, {g.G, 1 + g.KX + 8}, "params");
+  _check_shape(forecast, torch::kFloat32, {H, g.G}, "forecast");
+  _check_shape(forecast_se, torch::kFloat32, {H, g.G}, "forecast_se");
+  _check_f32(sigma2, "sigma2");
+  TORCH_CHECK(sigma2.numel() == g.G, "sigma2 must be [G]");
+  _check_shape(status, torch::kUInt8, {g.G}, "status");
+  const GroupfitForecastArgs a{
       yT.data_ptr<float>(), xc0.data_ptr<float>(), xc1.data_ptr<float>(),
       xc2.data_ptr<float>(), best_order.data_ptr<int>(),
       params.data_ptr<float>(), forecast.data_ptr<float>(),
       forecast_se.data_ptr<float>(), sigma2.data_ptr<float>(),
-      status.data_ptr<uint8_t>(), (int)T, (long long)G, (int)KX, (int)H,
-      stream.stream());
+      status.data_ptr<uint8_t>(), (int)g.T, (long long)g.G, (int)g.KX,
+      (int)H};
+  launch_groupfit_forecast(a, at::cuda::getCurrentHIPStream().stream());
   C10_HIP_KERNEL_LAUNCH_CHECK();
 }
 
@@ -311,28 +328,38 @@ void hwfit_final(torch::Tensor yT, torch::Tensor params,
   C10_HIP_KERNEL_LAUNCH_CHECK();
 }
 
-// Wc [n][G], wm [G] from the time-major panel (differenced d times,
-// centered with the per-group train mean).
+// Wc [S-d][G], wm [G] from the first S rows of the time-major panel
+// (differenced d times, centered with the per-group mean).
 void diff_center(torch::Tensor yT, torch::Tensor wc, torch::Tensor wm,
                  int64_t S, int64_t d) {
-  _check_f32(yT, "yT"); _check_f32(wc, "wc"); _check_f32(wm, "wm");
-  auto stream = at::cuda::getCurrentHIPStream();
+  _check_f32(yT, "yT");
+  TORCH_CHECK(yT.dim() == 2 && yT.size(1) >= 1, "yT must be [T][G>=1]");
+  const int64_t T = yT.size(0), G = yT.size(1);
+  TORCH_CHECK(d >= 0 && d <= 2, "d must be 0, 1 or 2");
+  TORCH_CHECK(S > d && S <= T && T <= (1 << 24),
+              "need d < S <= T <= 2^24");
+  _check_shape(wc, torch::kFloat32, {S - d, G}, "wc");
+  _check_shape(wm, torch::kFloat32, {G}, "wm");
   launch_diff_center(yT.data_ptr<float>(), wc.data_ptr<float>(),
-                     wm.data_ptr<float>(), yT.size(0), yT.size(1),
-                     (int)S, (int)d, stream.stream());
+                     wm.data_ptr<float>(), (int)T, (long long)G, (int)S,
+                     (int)d, at::cuda::getCurrentHIPStream().stream());
+  C10_HIP_KERNEL_LAUNCH_CHECK();
 }
 
 // beta[KX][G] = P[KX][n] @ wc[n][G] on the f32 matrix cores.
 void exog_project_mfma(torch::Tensor P, torch::Tensor wc,
                        torch::Tensor beta) {
-  _check_f32(P, "P"); _check_f32(wc, "wc"); _check_f32(beta, "beta");
-  TORCH_CHECK(P.size(1) == wc.size(0), "K mismatch");
-  TORCH_CHECK(beta.size(0) == P.size(0) && beta.size(1) == wc.size(1));
+  _check_f32(P, "P"); _check_f32(wc, "wc");
+  TORCH_CHECK(P.dim() == 2 && wc.dim() == 2 && wc.size(1) >= 1 &&
+                  P.size(1) == wc.size(0) && P.size(1) <= (1 << 24),
+              "P must be [KX][n] and wc [n][G>=1]");
   TORCH_CHECK(P.size(0) <= 16, "KX must fit one MFMA row tile");
-  auto stream = at::cuda::getCurrentHIPStream();
+  _check_shape(beta, torch::kFloat32, {P.size(0), wc.size(1)}, "beta");
   launch_exog_project_mfma(P.data_ptr<float>(), wc.data_ptr<float>(),
-                           beta.data_ptr<float>(), P.size(1), wc.size(1),
-                           P.size(0), stream.stream());
+                           beta.data_ptr<float>(), (int)P.size(1),
+                           (long long)wc.size(1), (int)P.size(0),
+                           at::cuda::getCurrentHIPStream().stream());
+  C10_HIP_KERNEL_LAUNCH_CHECK();
 }
 
 // ---------------------------------------------------------------- fused BN

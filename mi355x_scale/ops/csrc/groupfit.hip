@@ -1,42 +1,44 @@
-// Batched per-group ARIMAX fit for gfx950 (MI355X) — the N2 kernel.
+// Batched per-group ARIMAX fit, fitted values and forecast for gfx950
+// (MI355X).
 //
-// Replaces the reference's one-statsmodels-fit-per-Spark-task hot loop
-// (group_apply/02_Fine_Grained_Demand_Forecasting.py:441-450,472-481)
-// with a fixed-schedule estimator (see forecast/batched.py — the numpy
-// oracle these kernels are tested against):
-//   stage 1: OLS regression on shared exog design (host-precomputed
-//            pseudo-inverse / MFMA design GEMM -> per-group beta)
+// One statsmodels fit per group becomes a fixed-schedule estimator (see
+// forecast/batched.py, the numpy oracle these kernels are tested against):
+//   stage 0: w = diff^d(y), centered with its mean wm
+//   stage 1: OLS regression on the shared exog design -> per-group beta
+//            (precomputed by ops/csrc/mfma_project.hip, or in the kernel)
 //   stage 2: Yule-Walker + Levinson-Durbin long-AR -> innovations
-//   stage 3: lag-matrix normal equations (<=8x8), ridge + Cholesky,
+//   stage 3: lag-matrix normal equations (<= 8x8), ridge + Cholesky,
 //            stationarity shrinkage; one refinement pass (stage 4)
-//   stage 5: H-step validation forecast, integrated to y-units, MSE
+//   stage 5: H-step forecast, integrated to y-units
 //
-// MI355X-first decomposition: ONE GROUP PER LANE, 64 groups per wave,
-// one wave per workgroup. Global series are TIME-MAJOR [T][G] so every
-// per-timestep access is a fully coalesced 64-lane load.
+// ONE GROUP PER LANE, 64 groups per wave, one wave per workgroup. Global
+// series are TIME-MAJOR [T][G], so every per-timestep access is a fully
+// coalesced 64-lane load.
 //
-// STREAMING (round 2): every stage has <= 8-lag lookback, so the u/eps
-// series never materialize. Each pass re-derives u_t on the fly from
-// the y stream (1 coalesced load + KX fma) and carries 8-deep per-lane
-// REGISTER rings (constant-indexed under full unrolls — runtime-indexed
-// register arrays would spill, guide §5.4). The round-1 version staged
-// u/eps in LDS slabs (2 x S x 64 lanes fp32 ≈ 60 KB/block) and ran ONE
-// wave per CU; dropping the slabs leaves only the per-lane state block
-// (small matrices/vectors, 120 floats x 64 lanes = 30 KB) and lifts
-// occupancy to ~5 waves/CU. The extra y re-reads are noise: ~4 passes
-// x n x 4 B x G per candidate ≈ 190 MB at 8 TB/s HBM3E.
+// Nothing of length T is stored. Every stage looks back at most 8 lags, so
+// each pass re-derives u_t from the y stream (one coalesced load + KX fma)
+// and carries 8-deep per-lane REGISTER rings, constant-indexed under full
+// unrolls (a runtime-indexed register array goes to scratch). The only
+// per-lane memory is the LDS state block of the fit's small matrices and
+// vectors (120 floats x 64 lanes = 30 KB), which bounds the fit kernels at
+// 5 waves per CU; the forecast kernel holds its coefficients in registers
+// and uses no LDS. The y re-reads are cheap: about 4 passes x n x 4 B x G
+// per candidate.
 //
-// Design note on MFMA: the per-group normal equations are at most 8x8
-// built from ~120-step series — batching 64 groups per wave makes the
-// whole fit latency-bound, so matrix cores only help stage 1 (the
-// [KX,n]x[n,G] design GEMM, ops/csrc/mfma_project.hip), which both the
-// eval and final kernels take precomputed.
+// Three kernels share the pieces below: groupfit_eval_kernel (every group
+// x every candidate order -> validation MSE), groupfit_final_kernel (one
+// order per group on the whole series -> fitted values + coefficients)
+// and groupfit_forecast_kernel (stored coefficients -> forecast + standard
+// errors). The matrix cores only help stage 1; the per-group normal
+// equations are at most 8x8 over ~120 steps and latency-bound.
 
 #include <hip/hip_runtime.h>
 #include <math.h>
 
+#include "groupfit.h"
+
 #define WAVE 64
-#define MAXK 8          // p + q <= 8
+#define MAXK 8          // p + q <= 8, KX <= 8
 #define MAXM 7          // long-AR order cap
 #define RIDGE 1e-6f
 #define SHRINK 0.98f
@@ -112,10 +114,10 @@ __device__ void levinson(float* st, int lane, int M) {
 }
 
 // ---------------------------------------------------------------------
-// Streaming pass machinery. Each pass walks t = 0..S-1, re-deriving
-//   w_t  = diff^d(y)_t            (y0/y1 register ring)
+// The pieces of the recursion, each written once. With td = t - d:
+//   w_t  = diff^d(y)_t                      (diff_step, groupfit.h)
 //   u_td = (w_t - wm) - x_td . beta
-// and carries ur[j] = u_{td-1-j}, er[j] = e_{td-1-j} register rings
+// and ur[j] = u_{td-1-j}, er[j] = e_{td-1-j} are the register rings
 // (zero-filled: pre-sample lags are zero, matching the oracle).
 // ---------------------------------------------------------------------
 
@@ -123,23 +125,123 @@ __device__ void levinson(float* st, int lane, int M) {
   _Pragma("unroll") for (int _j = 7; _j > 0; --_j) r[_j] = r[_j - 1]; \
   r[0] = (v)
 
-// One streaming u-producer step. Returns u_td (only valid when t >= d).
-__device__ __forceinline__ float u_step(
-    const float* __restrict__ yT, const float* __restrict__ xc,
-    const float* st, int lane, long long g, long long G, int KX,
-    int d, int t, float wm, float* y0, float* y1) {
-  const float yv = yT[(long long)t * G + g];
-  float w;
-  if (d == 0) w = yv;
-  else if (d == 1) w = yv - *y0;
-  else w = yv - 2.0f * (*y0) + (*y1);
-  *y1 = *y0; *y0 = yv;
-  if (t < d) return 0.0f;
-  const int td = t - d;
+__device__ __forceinline__ void rings_clear(float* ur, float* er) {
+#pragma unroll
+  for (int j = 0; j < 8; ++j) { ur[j] = 0.0f; er[j] = 0.0f; }
+}
+
+// A lane's order, clamped to what the state block and the rings hold
+// (p, q <= 4, d <= 2). The host rejects anything else; for an order that
+// reaches a kernel through a device tensor the clamp turns an
+// out-of-bounds write into a well-defined wrong answer.
+struct Order { int p, d, q; };
+__device__ __forceinline__ Order load_order(const int* __restrict__ o) {
+  return {min(max(o[0], 0), 4), min(max(o[1], 0), 2), min(max(o[2], 0), 4)};
+}
+
+// The operand a{d} of differencing order d. A select, not an array: a
+// runtime-indexed array of pointers would go to scratch. A macro, not a
+// function: selected inside an inlined helper, the forecast kernel
+// allocates 66 VGPRs instead of 64 and loses a wave per SIMD.
+#define PICK_D(d, a) (((d) == 0) ? a##0 : ((d) == 1) ? a##1 : a##2)
+
+// The lane's beta in the LDS state block.
+struct LdsBeta {
+  const float* st;
+  int lane;
+};
+
+// Regression term x_row . beta of design row `row`, summed from 0 for
+// k = 0..KX-1. Two loop shapes for the two homes of beta: a runtime trip
+// count over LDS, and a full unroll with a predicate over registers, which
+// keeps the register array constant-indexed.
+__device__ __forceinline__ float reg_term(const float* __restrict__ xc,
+                                          long long row, const LdsBeta& b,
+                                          int KX) {
+  const float* st = b.st;
+  const int lane = b.lane;
   float reg = 0.0f;
-  for (int k = 0; k < KX; ++k)
-    reg += xc[(long long)td * KX + k] * st[SIDX(ST_BETA + k)];
-  return (w - wm) - reg;
+  for (int k = 0; k < KX; ++k) reg += xc[row * KX + k] * BETA(k);
+  return reg;
+}
+__device__ __forceinline__ float reg_term(const float* __restrict__ xc,
+                                          long long row,
+                                          const float (&beta)[MAXK],
+                                          int KX) {
+  float reg = 0.0f;
+#pragma unroll
+  for (int k = 0; k < MAXK; ++k)
+    if (k < KX) reg += xc[row * KX + k] * beta[k];
+  return reg;
+}
+
+__device__ __forceinline__ void load_arma(const float* st, int lane,
+                                          float* ph, float* th) {
+#pragma unroll
+  for (int i = 0; i < 4; ++i) { ph[i] = PHI(i); th[i] = THETA(i); }
+}
+
+// ARMA part of the prediction from the lag rings (coefs past p, q are 0).
+__device__ __forceinline__ float arma_dot(const float* ph, const float* th,
+                                          const float* ur, const float* er) {
+  return ph[0] * ur[0] + ph[1] * ur[1] + ph[2] * ur[2] + ph[3] * ur[3] +
+         th[0] * er[0] + th[1] * er[1] + th[2] * er[2] + th[3] * er[3];
+}
+
+// The innovation exists in two roundings, and each kernel keeps its own.
+// The fit (NE pass 1 and the final innovation pass of fit_lane) subtracts
+// term by term, as the oracle's _fit_arma_one does:
+__device__ __forceinline__ float innovation(float u, const float* ph,
+                                            const float* th,
+                                            const float* ur,
+                                            const float* er) {
+  float e = u;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) e -= ph[i] * ur[i] + th[i] * er[i];
+  return e;
+}
+// The fitted-value pass and the forecast's streaming pass need the
+// prediction acc itself and take e = u - acc from it. One in-sample step:
+// predicts from the lags, THEN pushes the current u and e. Returns e.
+__device__ __forceinline__ float insample_step(float w, float wm, float regx,
+                                               const float* ph,
+                                               const float* th, float* ur,
+                                               float* er, float& acc) {
+  acc = arma_dot(ph, th, ur, er);
+  const float u = (w - wm) - regx;
+  const float e = u - acc;
+  RING_SHIFT(ur, u);
+  RING_SHIFT(er, e);
+  return e;
+}
+
+// One out-of-sample step in w-space at design row `row`: the future u is
+// the ARMA part, the future e is 0. Returns w_pred.
+template <class Beta>
+__device__ __forceinline__ float forecast_step(const float* __restrict__ xc,
+                                               long long row,
+                                               const Beta& beta, int KX,
+                                               float wm, const float* ph,
+                                               const float* th, float* ur,
+                                               float* er) {
+  const float regx = reg_term(xc, row, beta, KX);
+  const float acc = arma_dot(ph, th, ur, er);
+  RING_SHIFT(ur, acc);
+  RING_SHIFT(er, 0.0f);
+  return wm + regx + acc;
+}
+
+// Streaming-pass skeleton: walks t = 0..S-1 of one lane's series from a
+// zeroed y ring, skips the d warm-up steps and calls body(td, w_td).
+template <class Body>
+__device__ __forceinline__ void stream_w(const float* __restrict__ yT,
+                                         long long g, long long G, int S,
+                                         int d, Body body) {
+  float y0 = 0.0f, y1 = 0.0f;
+  for (int t = 0; t < S; ++t) {
+    const float w = diff_step(d, yT[(long long)t * G + g], y0, y1);
+    if (t >= d) body(t - d, w);
+  }
 }
 
 // Core fit for one (group-lane, order): leaves ST_BETA/ST_PHI/ST_THETA
@@ -153,7 +255,6 @@ __device__ float fit_lane(
     const float* __restrict__ beta_pre,  // [KX][G] from the MFMA
     const float* __restrict__ wm_pre) {  // [G]     projection, or null
   const int n = S - d;
-  float y0, y1;
 
   // ---- stage 0: mean of the differenced series (pass only if needed)
   float wm;
@@ -161,16 +262,7 @@ __device__ float fit_lane(
     wm = wm_pre[g];
   } else {
     float wsum = 0.0f;
-    y0 = y1 = 0.0f;
-    for (int t = 0; t < S; ++t) {
-      const float yv = yT[(long long)t * G + g];
-      float w;
-      if (d == 0) w = yv;
-      else if (d == 1) w = yv - y0;
-      else w = yv - 2.0f * y0 + y1;
-      y1 = y0; y0 = yv;
-      if (t >= d) wsum += w;
-    }
+    stream_w(yT, g, G, S, d, [&](int, float w) { wsum += w; });
     wm = wsum / (float)n;
   }
 
@@ -183,30 +275,28 @@ __device__ float fit_lane(
     float bacc[MAXK];
 #pragma unroll
     for (int k = 0; k < MAXK; ++k) bacc[k] = 0.0f;
-    y0 = y1 = 0.0f;
-    for (int t = 0; t < S; ++t) {
-      const float yv = yT[(long long)t * G + g];
-      float w;
-      if (d == 0) w = yv;
-      else if (d == 1) w = yv - y0;
-      else w = yv - 2.0f * y0 + y1;
-      y1 = y0; y0 = yv;
-      if (t < d) continue;
-      const int td = t - d;
+    stream_w(yT, g, G, S, d, [&](int td, float w) {
       const float wcv = w - wm;
 #pragma unroll
       for (int k = 0; k < MAXK; ++k)
         if (k < KX) bacc[k] += PJ[(long long)k * n + td] * wcv;
-    }
+    });
 #pragma unroll
     for (int k = 0; k < MAXK; ++k)
       if (k < KX) BETA(k) = bacc[k];
   }
 
+  // every later pass streams u_td under the beta just stored
+  const LdsBeta beta{st, lane};
+  auto stream_u = [&](auto body) {
+    stream_w(yT, g, G, S, d, [&](int td, float w) {
+      body(td, (w - wm) - reg_term(xc, td, beta, KX));
+    });
+  };
+
 #pragma unroll
   for (int i = 0; i < 4; ++i) { PHI(i) = 0.0f; THETA(i) = 0.0f; }
-#pragma unroll
-  for (int j = 0; j < 8; ++j) { ur[j] = 0.0f; er[j] = 0.0f; }
+  rings_clear(ur, er);
 
   const int K = p + q;
   const bool lane_q = q > 0;
@@ -221,16 +311,13 @@ __device__ float fit_lane(
     float r[MAXM + 1];
 #pragma unroll
     for (int k = 0; k <= MAXM; ++k) r[k] = 0.0f;
-    y0 = y1 = 0.0f;
-    for (int t = 0; t < S; ++t) {
-      const float u = u_step(yT, xc, st, lane, g, G, KX, d, t, wm, &y0, &y1);
-      if (t < d) continue;
+    stream_u([&](int, float u) {
       r[0] += u * u;
 #pragma unroll
       for (int k = 1; k <= MAXM; ++k)
         if (k <= M) r[k] += u * ur[k - 1];
       RING_SHIFT(ur, u);
-    }
+    });
     if (lane_q) {
 #pragma unroll
       for (int k = 0; k <= MAXM; ++k)
@@ -252,36 +339,29 @@ __device__ float fit_lane(
     // the refinement pass nor the final innovation pass (its theta
     // terms are zero, so the e-ring is never consumed)
     const int npass = any_q ? 2 : 1;
+    float phr[4], thr[4];
     for (int pass = 0; pass < npass; ++pass) {
       const bool solve_here = lane_K && (pass == 0 || lane_q);
       // coefs for this pass's innovation recursion
-      float alr[MAXM], phr[4], thr[4];
+      float alr[MAXM];
 #pragma unroll
       for (int i = 0; i < MAXM; ++i)
         alr[i] = (lane_q && pass == 0 && i < M) ? st[SIDX(ST_AL + i)] : 0.0f;
-#pragma unroll
-      for (int i = 0; i < 4; ++i) { phr[i] = PHI(i); thr[i] = THETA(i); }
+      load_arma(st, lane, phr, thr);
       if (solve_here) {
         for (int i = 0; i < 64; ++i) st[SIDX(ST_A + i)] = 0.0f;
         for (int i = 0; i < 8; ++i) st[SIDX(ST_C + i)] = 0.0f;
       }
-#pragma unroll
-      for (int j = 0; j < 8; ++j) { ur[j] = 0.0f; er[j] = 0.0f; }
-      y0 = y1 = 0.0f;
-      for (int t = 0; t < S; ++t) {
-        const float u = u_step(yT, xc, st, lane, g, G, KX, d, t, wm,
-                               &y0, &y1);
-        if (t < d) continue;
-        const int td = t - d;
+      rings_clear(ur, er);
+      stream_u([&](int td, float u) {
         // innovation under this pass's recursion
-        float e = u;
+        float e;
         if (pass == 0) {
+          e = u;
 #pragma unroll
           for (int i = 0; i < MAXM; ++i) e -= alr[i] * ur[i];
         } else {
-#pragma unroll
-          for (int i = 0; i < 4; ++i)
-            e -= phr[i] * ur[i] + thr[i] * er[i];
+          e = innovation(u, phr, thr, ur, er);
         }
         if (solve_here && td >= m) {
 #pragma unroll
@@ -299,7 +379,7 @@ __device__ float fit_lane(
         }
         RING_SHIFT(ur, u);
         RING_SHIFT(er, e);
-      }
+      });
       if (solve_here) {
         float tr = 0.0f;
         for (int i = 0; i < K; ++i) tr += st[SIDX(ST_A + i * 8 + i)];
@@ -334,23 +414,13 @@ __device__ float fit_lane(
     // final innovation pass under the final coefs (leaves the rings at
     // the end of the series for stage 5 / the fitted-value writer)
     if (any_q) {
-      float phr[4], thr[4];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) { phr[i] = PHI(i); thr[i] = THETA(i); }
-#pragma unroll
-      for (int j = 0; j < 8; ++j) { ur[j] = 0.0f; er[j] = 0.0f; }
-      y0 = y1 = 0.0f;
-      for (int t = 0; t < S; ++t) {
-        const float u = u_step(yT, xc, st, lane, g, G, KX, d, t, wm,
-                               &y0, &y1);
-        if (t < d) continue;
-        float e = u;
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-          e -= phr[i] * ur[i] + thr[i] * er[i];
+      load_arma(st, lane, phr, thr);
+      rings_clear(ur, er);
+      stream_u([&](int, float u) {
+        const float e = innovation(u, phr, thr, ur, er);
         RING_SHIFT(ur, u);
         RING_SHIFT(er, e);
-      }
+      });
     }
   }
 
@@ -362,19 +432,20 @@ __device__ float fit_lane(
   return wm;
 }
 
+// Candidate evaluation: every group fits every order of the list on rows
+// 0..S-1 and is scored on the H = T - S rows after them.
 extern "C" __global__ __launch_bounds__(WAVE) void groupfit_eval_kernel(
     const float* __restrict__ yT,
     const float* __restrict__ xc0, const float* __restrict__ xc1,
     const float* __restrict__ xc2,
     const float* __restrict__ pj0, const float* __restrict__ pj1,
     const float* __restrict__ pj2,
-    const int* __restrict__ orders,       // [C][3]
-    float* __restrict__ mse,              // [C][G]
-    unsigned char* __restrict__ statusv,  // [C][G]
+    const int* __restrict__ orders, float* __restrict__ mse,
+    unsigned char* __restrict__ status,
     const float* __restrict__ b0, const float* __restrict__ b1,
-    const float* __restrict__ b2,         // [KX][G] per d, or null
+    const float* __restrict__ b2,
     const float* __restrict__ w0, const float* __restrict__ w1,
-    const float* __restrict__ w2,         // [G] per d, or null
+    const float* __restrict__ w2,
     int T, long long G, int S, int C, int KX) {
   __shared__ float st[NSTATE * WAVE];
   const int lane = threadIdx.x;
@@ -382,40 +453,30 @@ extern "C" __global__ __launch_bounds__(WAVE) void groupfit_eval_kernel(
   const bool active = g < G;
   const long long gg = active ? g : (G - 1);
   const int H = T - S;
-  float ur[8], er[8];
+  const LdsBeta beta{st, lane};
+  float ur[8], er[8], ph[4], th[4];
 
   for (int c = 0; c < C; ++c) {
-    const int p = orders[c * 3 + 0];
-    const int d = orders[c * 3 + 1];
-    const int q = orders[c * 3 + 2];
-    const float* xc = (d == 0) ? xc0 : (d == 1) ? xc1 : xc2;
-    const float* PJ = (d == 0) ? pj0 : (d == 1) ? pj1 : pj2;
+    const Order o = load_order(orders + c * 3);
+    const int p = o.p, d = o.d, q = o.q;
+    const float* xc = PICK_D(d, xc);
     const int n = S - d;
-
-    const float* bpre = (d == 0) ? b0 : (d == 1) ? b1 : b2;
-    const float* wpre = (d == 0) ? w0 : (d == 1) ? w1 : w2;
     bool ok;
-    const float wm = fit_lane(yT, xc, PJ, st, lane, gg, G, S, KX,
-                              p, d, q, &ok, ur, er, bpre, wpre);
+    const float wm = fit_lane(
+        yT, xc, PICK_D(d, pj), st, lane, gg, G, S, KX,
+        p, d, q, &ok, ur, er, PICK_D(d, b),
+        PICK_D(d, w));
 
     // ---- stage 5: validation forecast + MSE (rings hold u/e at n-1-j)
-    float u0 = ur[0], u1 = ur[1], u2 = ur[2], u3 = ur[3];
-    float e0 = er[0], e1 = er[1], e2 = er[2], e3 = er[3];
-    const float ph0 = PHI(0), ph1 = PHI(1), ph2 = PHI(2), ph3 = PHI(3);
-    const float th0 = THETA(0), th1 = THETA(1), th2 = THETA(2),
-                th3 = THETA(3);
+    load_arma(st, lane, ph, th);
     float yl1 = yT[(long long)(S - 1) * G + gg];
     float yl2 = (S - 2 >= 0) ? yT[(long long)(S - 2) * G + gg] : 0.f;
     float sse = 0.0f;
     for (int h = 0; h < H; ++h) {
-      float reg = 0.0f;
-      for (int k = 0; k < KX; ++k)
-        reg += xc[(long long)(n + h) * KX + k] * BETA(k);
-      const float acc = ph0 * u0 + ph1 * u1 + ph2 * u2 + ph3 * u3 +
-                        th0 * e0 + th1 * e1 + th2 * e2 + th3 * e3;
-      const float w_pred = wm + reg + acc;
-      u3 = u2; u2 = u1; u1 = u0; u0 = acc;
-      e3 = e2; e2 = e1; e1 = e0; e0 = 0.0f;
+      const float w_pred = forecast_step(xc, n + h, beta, KX, wm, ph, th, ur,
+                                         er);
+      // d = 1 adds to a running y here, while the forecast kernel sums
+      // w_pred first; merging the two would change the MSE bits
       float y_pred;
       if (d == 0) y_pred = w_pred;
       else if (d == 1) { y_pred = yl1 + w_pred; yl2 = yl1; yl1 = y_pred; }
@@ -428,86 +489,65 @@ extern "C" __global__ __launch_bounds__(WAVE) void groupfit_eval_kernel(
     if (active) {
       const bool fin = ok && isfinite(m);
       mse[(long long)c * G + g] = fin ? m : INFINITY;
-      statusv[(long long)c * G + g] = fin ? 1 : 0;
+      status[(long long)c * G + g] = fin ? 1 : 0;
     }
   }
 }
 
 // Final fit: per-group chosen order (may differ per lane — the passes
-// are wave-voted, per-lane work predicated). Writes one-step-ahead
-// fitted values [T][G] in y-units, per-group coefficient vector
-// (wm, beta[KX], phi[4], theta[4]) and status. beta/wm precomputed by
-// the MFMA projection over the FULL-series design when given.
+// are wave-voted, per-lane work predicated) on the whole series. Writes
+// one-step-ahead fitted values, the coefficient vector and status.
 extern "C" __global__ __launch_bounds__(WAVE) void groupfit_final_kernel(
     const float* __restrict__ yT,
     const float* __restrict__ xc0, const float* __restrict__ xc1,
     const float* __restrict__ xc2,
     const float* __restrict__ pj0, const float* __restrict__ pj1,
     const float* __restrict__ pj2,
-    const int* __restrict__ best_order,  // [G][3]
-    float* __restrict__ fitted,          // [T][G]
-    float* __restrict__ params,          // [G][1+KX+8]
-    unsigned char* __restrict__ statusv, // [G]
+    const int* __restrict__ best_order, float* __restrict__ fitted,
+    float* __restrict__ params, unsigned char* __restrict__ status,
     const float* __restrict__ b0, const float* __restrict__ b1,
-    const float* __restrict__ b2,        // [KX][G] per d, or null
+    const float* __restrict__ b2,
     const float* __restrict__ w0, const float* __restrict__ w1,
-    const float* __restrict__ w2,        // [G] per d, or null
+    const float* __restrict__ w2,
     int T, long long G, int KX) {
   __shared__ float st[NSTATE * WAVE];
   const int lane = threadIdx.x;
   const long long g = (long long)blockIdx.x * WAVE + lane;
   const bool active = g < G;
   const long long gg = active ? g : (G - 1);
-  const int p = best_order[gg * 3 + 0];
-  const int d = best_order[gg * 3 + 1];
-  const int q = best_order[gg * 3 + 2];
-  const float* xc = (d == 0) ? xc0 : (d == 1) ? xc1 : xc2;
-  const float* PJ = (d == 0) ? pj0 : (d == 1) ? pj1 : pj2;
-  const float* bpre = (d == 0) ? b0 : (d == 1) ? b1 : b2;
-  const float* wpre = (d == 0) ? w0 : (d == 1) ? w1 : w2;
-  const int S = T;  // final fit uses the whole series
-  float ur[8], er[8];
+  const Order o = load_order(best_order + gg * 3);
+  const int p = o.p, d = o.d, q = o.q;
+  const float* xc = PICK_D(d, xc);
+  float ur[8], er[8], ph[4], th[4];
 
   bool ok;
-  const float wm = fit_lane(yT, xc, PJ, st, lane, gg, G, S, KX,
-                            p, d, q, &ok, ur, er, bpre, wpre);
+  const float wm = fit_lane(
+      yT, xc, PICK_D(d, pj), st, lane, gg, G, T, KX,
+      p, d, q, &ok, ur, er, PICK_D(d, b),
+      PICK_D(d, w));
 
-  // Fitted-value pass: stream t, predict from the lag rings, THEN push
-  // the current u/e (one-step-ahead: prediction at t uses lags only).
+  // Fitted-value pass. Not through stream_w: the d warm-up steps write
+  // y itself, and the integration needs the y ring from before the step.
   {
-    const float ph0 = PHI(0), ph1 = PHI(1), ph2 = PHI(2), ph3 = PHI(3);
-    const float th0 = THETA(0), th1 = THETA(1), th2 = THETA(2),
-                th3 = THETA(3);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) { ur[j] = 0.0f; er[j] = 0.0f; }
+    const LdsBeta beta{st, lane};
+    load_arma(st, lane, ph, th);
+    rings_clear(ur, er);
     float y0 = 0.f, y1 = 0.f;
     for (int t = 0; t < T; ++t) {
       const float yv = yT[(long long)t * G + gg];
       const float yl1 = y0, yl2 = y1;
-      float w;
-      if (d == 0) w = yv;
-      else if (d == 1) w = yv - y0;
-      else w = yv - 2.0f * y0 + y1;
-      y1 = y0; y0 = yv;
+      const float w = diff_step(d, yv, y0, y1);
       float out;
       if (t < d) {
         out = yv;
       } else {
-        const int td = t - d;
-        float regx = 0.0f;
-        for (int k = 0; k < KX; ++k)
-          regx += xc[(long long)td * KX + k] * BETA(k);
-        const float acc = ph0 * ur[0] + ph1 * ur[1] + ph2 * ur[2] +
-                          ph3 * ur[3] + th0 * er[0] + th1 * er[1] +
-                          th2 * er[2] + th3 * er[3];
+        const float regx = reg_term(xc, t - d, beta, KX);
+        float acc;
+        insample_step(w, wm, regx, ph, th, ur, er, acc);
         const float what = wm + regx + acc;
         if (d == 0) out = what;
         else if (d == 1) out = yl1 + what;
         else out = 2.0f * yl1 - yl2 + what;
-        const float u = (w - wm) - regx;
-        const float e = u - acc;
-        RING_SHIFT(ur, u);
-        RING_SHIFT(er, e);
       }
       if (active) fitted[(long long)t * G + g] = out;
     }
@@ -521,42 +561,37 @@ extern "C" __global__ __launch_bounds__(WAVE) void groupfit_final_kernel(
       pp[1 + KX + i] = PHI(i);
       pp[1 + KX + 4 + i] = THETA(i);
     }
-    statusv[g] = ok ? 1 : 0;
+    status[g] = ok ? 1 : 0;
   }
 }
 
 // Out-of-sample forecast from STORED coefficients: no fitting and no LDS
 // state block. wm, beta, phi, theta come from `params` into registers; one
-// streaming pass over t rebuilds the end-of-series u/e rings (the
-// fitted-value recursion of the final kernel) and accumulates
+// streaming pass of insample_step rebuilds the end-of-series u/e rings and
+// accumulates
 //   sigma2 = 1/(n-m) sum_{td>=m} e_td^2,   m = max(p,q);
-// then H steps of the forecast recursion, integrated to y-units, next to
-// the psi-weight recursion of the ARIMA(p,d,q) process
+// then H forecast_steps, integrated to y-units, next to the psi-weight
+// recursion of the ARIMA(p,d,q) process
 //   1 - sum a_k B^k = (1 - sum phi_i B^i)(1-B)^d        (p + d <= 6)
 //   psi_0 = 1,  psi_j = theta_j [j<=q] + sum_k a_k psi_{j-k}
 //   se_h  = sqrt(sigma2 * sum_{j<=h} psi_j^2).
-// xc{d} are the STACKED designs: T-d history rows, then H future rows.
-// Orders are per lane; they are clamped to p,q <= 4, d <= 2, so a lane
-// always has n - m >= T - 6 residuals and reads inside xc{d}.
+// Orders are per lane; clamped, a lane always has n - m >= T - 6 residuals
+// and reads inside xc{d}.
 extern "C" __global__ __launch_bounds__(WAVE) void groupfit_forecast_kernel(
     const float* __restrict__ yT,
     const float* __restrict__ xc0, const float* __restrict__ xc1,
-    const float* __restrict__ xc2,        // [T+H-d][KX]
-    const int* __restrict__ best_order,   // [G][3]
-    const float* __restrict__ params,     // [G][1+KX+8]
-    float* __restrict__ forecast,         // [H][G]
-    float* __restrict__ forecast_se,      // [H][G]
-    float* __restrict__ sigma2v,          // [G]
-    unsigned char* __restrict__ statusv,  // [G]
+    const float* __restrict__ xc2,
+    const int* __restrict__ best_order, const float* __restrict__ params,
+    float* __restrict__ forecast, float* __restrict__ forecast_se,
+    float* __restrict__ sigma2v, unsigned char* __restrict__ status,
     int T, long long G, int KX, int H) {
   const int lane = threadIdx.x;
   const long long g = (long long)blockIdx.x * WAVE + lane;
   const bool active = g < G;
   const long long gg = active ? g : (G - 1);
-  const int p = min(max(best_order[gg * 3 + 0], 0), 4);
-  const int d = min(max(best_order[gg * 3 + 1], 0), 2);
-  const int q = min(max(best_order[gg * 3 + 2], 0), 4);
-  const float* xc = (d == 0) ? xc0 : (d == 1) ? xc1 : xc2;
+  const Order o = load_order(best_order + gg * 3);
+  const int p = o.p, d = o.d, q = o.q;
+  const float* xc = PICK_D(d, xc);
   const int n = T - d;
   const int m = max(p, q);
 
@@ -572,34 +607,22 @@ extern "C" __global__ __launch_bounds__(WAVE) void groupfit_forecast_kernel(
   }
 
   // ---- streaming pass: end-of-series rings + residual sum of squares.
-  // The y load of step t+1 is issued before the recursion of step t.
+  // Not through stream_w: the y load of step t+1 is issued before the
+  // recursion of step t.
   float ur[8], er[8];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) { ur[j] = 0.0f; er[j] = 0.0f; }
+  rings_clear(ur, er);
   float y0 = 0.0f, y1 = 0.0f, sse = 0.0f;
   float ynext = yT[gg];
   for (int t = 0; t < T; ++t) {
     const float yv = ynext;
     if (t + 1 < T) ynext = yT[(long long)(t + 1) * G + gg];
-    float w;
-    if (d == 0) w = yv;
-    else if (d == 1) w = yv - y0;
-    else w = yv - 2.0f * y0 + y1;
-    y1 = y0; y0 = yv;
+    const float w = diff_step(d, yv, y0, y1);
     if (t >= d) {
       const int td = t - d;
-      float regx = 0.0f;
-#pragma unroll
-      for (int k = 0; k < MAXK; ++k)
-        if (k < KX) regx += xc[(long long)td * KX + k] * beta[k];
-      const float acc = ph[0] * ur[0] + ph[1] * ur[1] + ph[2] * ur[2] +
-                        ph[3] * ur[3] + th[0] * er[0] + th[1] * er[1] +
-                        th[2] * er[2] + th[3] * er[3];
-      const float u = (w - wm) - regx;
-      const float e = u - acc;
+      const float regx = reg_term(xc, td, beta, KX);
+      float acc;
+      const float e = insample_step(w, wm, regx, ph, th, ur, er, acc);
       if (td >= m) sse += e * e;
-      RING_SHIFT(ur, u);
-      RING_SHIFT(er, e);
     }
   }
   const float sigma2 = sse / (float)(n - m);
@@ -631,16 +654,8 @@ extern "C" __global__ __launch_bounds__(WAVE) void groupfit_forecast_kernel(
   float wsum = 0.0f;
   bool fin = isfinite(sigma2);
   for (int h = 0; h < H; ++h) {
-    float regx = 0.0f;
-#pragma unroll
-    for (int k = 0; k < MAXK; ++k)
-      if (k < KX) regx += xc[(long long)(n + h) * KX + k] * beta[k];
-    const float acc = ph[0] * ur[0] + ph[1] * ur[1] + ph[2] * ur[2] +
-                      ph[3] * ur[3] + th[0] * er[0] + th[1] * er[1] +
-                      th[2] * er[2] + th[3] * er[3];
-    const float w_pred = wm + regx + acc;
-    RING_SHIFT(ur, acc);         // future u = ARMA part, future e = 0
-    RING_SHIFT(er, 0.0f);
+    const float w_pred = forecast_step(xc, n + h, beta, KX, wm, ph, th, ur,
+                                       er);
     // d = 1 sums the small w_pred first and adds y_{T-1} once, as the
     // oracle does: one rounding at the size of y, not one per step
     float y_pred;
@@ -670,46 +685,36 @@ extern "C" __global__ __launch_bounds__(WAVE) void groupfit_forecast_kernel(
   }
   if (active) {
     sigma2v[g] = sigma2;
-    statusv[g] = fin ? 1 : 0;
+    status[g] = fin ? 1 : 0;
   }
 }
 
-extern "C" void launch_groupfit_forecast(
-    const float* yT, const float* xc0, const float* xc1, const float* xc2,
-    const int* best_order, const float* params, float* forecast,
-    float* forecast_se, float* sigma2, unsigned char* statusv,
-    int T, long long G, int KX, int H, hipStream_t stream) {
-  const int blocks = (int)((G + WAVE - 1) / WAVE);
-  hipLaunchKernelGGL(groupfit_forecast_kernel, dim3(blocks), dim3(WAVE), 0,
-                     stream, yT, xc0, xc1, xc2, best_order, params, forecast,
-                     forecast_se, sigma2, statusv, T, G, KX, H);
+// One wave of 64 groups per block. The kernels take their operands one by
+// one so that the pointers are __restrict__ kernel arguments: read through
+// a struct they lose that, and the uniform loads of the orders and the
+// design rows stop being scalar loads.
+#define WAVE_GRID(G) dim3((int)(((G) + WAVE - 1) / WAVE)), dim3(WAVE), 0
+
+extern "C" void launch_groupfit_eval(const GroupfitEvalArgs& a,
+                                     hipStream_t stream) {
+  hipLaunchKernelGGL(groupfit_eval_kernel, WAVE_GRID(a.G), stream, a.yT,
+                     a.xc0, a.xc1, a.xc2, a.pj0, a.pj1, a.pj2, a.orders,
+                     a.mse, a.status, a.b0, a.b1, a.b2, a.w0, a.w1, a.w2,
+                     a.T, a.G, a.S, a.C, a.KX);
 }
 
-extern "C" void launch_groupfit_eval(
-    const float* yT, const float* xc0, const float* xc1, const float* xc2,
-    const float* pj0, const float* pj1, const float* pj2, const int* orders,
-    float* mse, unsigned char* statusv,
-    const float* b0, const float* b1, const float* b2,
-    const float* w0, const float* w1, const float* w2,
-    int T, long long G, int S, int C,
-    int KX, hipStream_t stream) {
-  const int blocks = (int)((G + WAVE - 1) / WAVE);
-  hipLaunchKernelGGL(groupfit_eval_kernel, dim3(blocks), dim3(WAVE), 0,
-                     stream, yT, xc0, xc1, xc2, pj0, pj1, pj2, orders, mse,
-                     statusv, b0, b1, b2, w0, w1, w2, T, G, S, C, KX);
+extern "C" void launch_groupfit_final(const GroupfitFinalArgs& a,
+                                      hipStream_t stream) {
+  hipLaunchKernelGGL(groupfit_final_kernel, WAVE_GRID(a.G), stream, a.yT,
+                     a.xc0, a.xc1, a.xc2, a.pj0, a.pj1, a.pj2, a.best_order,
+                     a.fitted, a.params, a.status, a.b0, a.b1, a.b2, a.w0,
+                     a.w1, a.w2, a.T, a.G, a.KX);
 }
 
-extern "C" void launch_groupfit_final(
-    const float* yT, const float* xc0, const float* xc1, const float* xc2,
-    const float* pj0, const float* pj1, const float* pj2,
-    const int* best_order, float* fitted, float* params,
-    unsigned char* statusv,
-    const float* b0, const float* b1, const float* b2,
-    const float* w0, const float* w1, const float* w2,
-    int T, long long G, int KX, hipStream_t stream) {
-  const int blocks = (int)((G + WAVE - 1) / WAVE);
-  hipLaunchKernelGGL(groupfit_final_kernel, dim3(blocks), dim3(WAVE), 0,
-                     stream, yT, xc0, xc1, xc2, pj0, pj1, pj2, best_order,
-                     fitted, params, statusv, b0, b1, b2, w0, w1, w2,
-                     T, G, KX);
+extern "C" void launch_groupfit_forecast(const GroupfitForecastArgs& a,
+                                         hipStream_t stream) {
+  hipLaunchKernelGGL(groupfit_forecast_kernel, WAVE_GRID(a.G), stream, a.yT,
+                     a.xc0, a.xc1, a.xc2, a.best_order, a.params,
+                     a.forecast, a.forecast_se, a.sigma2, a.status, a.T,
+                     a.G, a.KX, a.H);
 }

@@ -18,6 +18,8 @@
 
 #include <hip/hip_runtime.h>
 
+#include "groupfit.h"   // diff_step
+
 #define WAVE 64
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -32,12 +34,7 @@ extern "C" __global__ __launch_bounds__(256) void diff_center_kernel(
   const int n = S - d;
   float y0 = 0.f, y1 = 0.f, sum = 0.f;
   for (int t = 0; t < S; ++t) {
-    const float yv = yT[(long long)t * G + g];
-    float w;
-    if (d == 0) w = yv;
-    else if (d == 1) w = yv - y0;
-    else w = yv - 2.0f * y0 + y1;
-    y1 = y0; y0 = yv;
+    const float w = diff_step(d, yT[(long long)t * G + g], y0, y1);
     if (t >= d) {
       wc[(long long)(t - d) * G + g] = w;
       sum += w;

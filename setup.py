@@ -58,6 +58,7 @@ setup(
         CUDAExtension(
             name="mi355x_scale.ops._C",
             sources=SRC,
+            depends=["mi355x_scale/ops/csrc/groupfit.h"],
             extra_compile_args={
                 "cxx": ["-O3"],
                 "nvcc": ["-O3", "--offload-arch=gfx950"],

@@ -290,6 +290,37 @@ def test_forecast_gpu_validates_on_the_host():
             batched_forecast_gpu(**kw)
 
 
+def test_orders_are_validated_on_the_host():
+    """Every entry point that takes orders raises ValueError for an order
+    the kernels do not hold, before the extension is required; every order
+    the project itself uses passes."""
+    from mi355x_scale.forecast.batched import (_check_orders,
+                                               batched_eval_gpu,
+                                               batched_fit_gpu)
+    y, exog = gk._panel()
+    y = y[:4]
+    fx = _future_exog(7)
+    params = np.zeros((4, NPAR), dtype=np.float32)
+    for bad in [(5, 0, 0), (0, 3, 0), (0, 0, 5), (-1, 0, 0), (1, 1),
+                (1.5, 0, 0), (1, 0, 0, 0), 3, ("a", 0, 0)]:
+        orders = [(1, 0, 0), bad]
+        with pytest.raises(ValueError, match="order"):
+            batched_eval_gpu(y, exog, orders, gk.S_EVAL)
+        with pytest.raises(ValueError, match="order"):
+            batched_fit_gpu(y, exog, orders, gk.S_EVAL)
+        if np.shape(bad) == (3,) and not isinstance(bad[0], str):
+            best = np.array([(1, 1, 1)] * 3 + [bad])
+            with pytest.raises(ValueError, match="order"):
+                batched_forecast_gpu(y, exog, fx, best, params)
+    for S in (8, gk.T_FULL):                 # 8 < train_len < T
+        with pytest.raises(ValueError, match="train_len"):
+            batched_eval_gpu(y, exog, [(1, 0, 0)], S)
+    _check_orders(gk.DEFAULT_GPU_ORDERS)
+    _check_orders(gk.ALL)
+    _check_orders(np.array(gk.ALL, dtype=np.int32).tolist())
+    _check_orders([])
+
+
 def test_pandas_path_appends_future_rows_and_intervals():
     """(6) 2 groups, max_evals=3, forecast_steps=4, interval=0.9."""
     df = generate_demand_data(n_products=1, skus_per_product=2, n_weeks=120)

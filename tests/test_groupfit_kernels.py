@@ -727,3 +727,125 @@ def test_gpu_exog_project_mfma(G):
             worst = max(worst, dev)
             assert dev <= 1.0, (n, kx, dev)
     print(f"exog_project_mfma G={G}: worst={worst:.3g} of its bound")
+
+
+# ------------------------------------------------- (h) the binding checks
+def _binding_args(S, G=G_FULL, C=2):
+    """Valid operands of ``groupfit_eval`` (S < T) / ``groupfit_final``
+    (S = T) on the panel, outputs canaried: (args by name, call)."""
+    import torch
+    from mi355x_scale.forecast.batched import _designs_to_gpu, _to_yT
+    from mi355x_scale.ops import _C
+    final = S == T_FULL
+    xs, ps = _designs_to_gpu(_designs(S), "cuda")
+    bufs = _Bufs()
+    a = dict(yT=_to_yT(_panel()[0][:G], "cuda"))
+    for d in range(3):
+        a[f"xc{d}"], a[f"pj{d}"] = xs[d], ps[d]
+        a[f"b{d}"] = torch.zeros((KX, G), device="cuda")
+        a[f"w{d}"] = torch.zeros((G,), device="cuda")
+    rows = G if final else C
+    a["orders"] = torch.ones((rows, 3), dtype=torch.int32, device="cuda")
+    if final:
+        a["fitted"] = bufs.out("fitted", (T_FULL, G))
+        a["params"] = bufs.out("params", (G, NPAR))
+        a["status"] = bufs.out("status", (G,), torch.uint8)
+        outs = ("fitted", "params", "status")
+    else:
+        a["mse"] = bufs.out("mse", (C, G))
+        a["status"] = bufs.out("status", (C, G), torch.uint8)
+        outs = ("mse", "status")
+
+    def call(**change):
+        k = dict(a, **change)
+        head = [k[n] for n in ("yT", "xc0", "xc1", "xc2", "pj0", "pj1",
+                               "pj2", "orders") + outs]
+        tail = [k[f"{n}{d}"] for n in "bw" for d in range(3)]
+        if final:
+            _C.groupfit_final(*head, *tail)
+        else:
+            _C.groupfit_eval(*head, S, *tail)
+        torch.cuda.synchronize()
+
+    def untouched():
+        bufs.check()
+        return all((full == canary).all().item()
+                   for full, _, canary in bufs.bufs.values())
+
+    return a, call, untouched
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("S", [S_EVAL, T_FULL], ids=["eval", "final"])
+def test_gpu_fit_bindings_reject_bad_operands(S):
+    """(h) ``groupfit_eval`` / ``groupfit_final`` raise before any launch
+    for each malformed operand, one at a time, and leave the canaried
+    outputs as they were; the stacked designs of a forecast (more rows
+    than T - d) are accepted."""
+    import torch
+    G = G_FULL
+    a, call, untouched = _binding_args(S)
+    orders4 = torch.ones((a["orders"].shape[0], 4), dtype=torch.int32,
+                         device="cuda")
+    nine = torch.zeros((T_FULL, 9), device="cuda")
+    bad = {
+        "xc1 one row short": dict(xc1=a["xc1"][:T_FULL - 2].contiguous()),
+        "pj2 with S-1 columns": dict(pj2=torch.zeros((KX, S - 1),
+                                                     device="cuda")),
+        "b0 [KX][G-1]": dict(b0=torch.zeros((KX, G - 1), device="cuda")),
+        "w1 [G+1]": dict(w1=torch.zeros((G + 1,), device="cuda")),
+        "non-contiguous orders": dict(orders=orders4[:, :3]),
+        "status length": dict(status=torch.full(
+            (a["status"].numel() + 1,), 173, dtype=torch.uint8,
+            device="cuda")),
+        "KX = 9": dict(xc0=nine, xc1=nine[1:].contiguous(),
+                       xc2=nine[2:].contiguous()),
+    }
+    if S == T_FULL:
+        bad["params one column short"] = dict(
+            params=torch.full((G, NPAR - 1), -12345.0, device="cuda"))
+    else:
+        bad["mse one row short"] = dict(
+            mse=torch.full((1, G), -12345.0, device="cuda"))
+    for what, change in bad.items():
+        print(what)
+        with pytest.raises(RuntimeError):
+            call(**change)
+        assert untouched(), what
+    # three more design rows than the fit reads: accepted
+    more = {f"xc{d}": torch.cat([a[f"xc{d}"], a[f"xc{d}"][:3]]).contiguous()
+            for d in range(3)}
+    call(**more)
+    assert not untouched()
+
+
+@pytest.mark.gpu
+def test_gpu_projection_bindings_reject_bad_operands():
+    """(h) ``diff_center`` and ``exog_project_mfma`` raise before any
+    launch for a wc one row short, a wm one element short, d = 3 and a
+    beta of [KX][G-1]; the canaried outputs stay as they were."""
+    import torch
+    from mi355x_scale.forecast.batched import _designs_to_gpu, _to_yT
+    from mi355x_scale.ops import _C
+    G, S, d = G_FULL, S_EVAL, 1
+    yT = _to_yT(_panel()[0], "cuda")
+    _, ps = _designs_to_gpu(_designs(S), "cuda")
+    bufs = _Bufs()
+    wc = bufs.out("wc", (S - d, G))
+    wm = bufs.out("wm", (G,))
+    beta = bufs.out("beta", (KX, G))
+    short_wc = bufs.out("short_wc", (S - d - 1, G))
+    short_wm = bufs.out("short_wm", (G - 1,))
+    wc3 = bufs.out("wc3", (S - 3, G))
+    short_beta = bufs.out("short_beta", (KX, G - 1))
+    for args in ((yT, short_wc, wm, S, d), (yT, wc, short_wm, S, d),
+                 (yT, wc3, wm, S, 3), (yT, wc, wm, S, -1),
+                 (yT, wc, wm, T_FULL + 1, d)):
+        with pytest.raises(RuntimeError):
+            _C.diff_center(*args)
+    for args in ((ps[d], wc, short_beta), (ps[0], wc, beta)):
+        with pytest.raises(RuntimeError):
+            _C.exog_project_mfma(*args)
+    bufs.check()
+    for name, (full, _, canary) in bufs.bufs.items():
+        assert (full == canary).all().item(), name
