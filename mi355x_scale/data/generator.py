@@ -310,6 +310,36 @@ def decode_jpeg_batch(pdf: pd.DataFrame,
     return {"image": out, "label": pdf["label"].to_numpy()}
 
 
+def decode_jpeg_canvas(pdf: pd.DataFrame,
+                       canvas_hw: Tuple[int, int] = (512, 512)
+                       ) -> Dict[str, np.ndarray]:
+    """Decode-only transform for device-side resampling: JPEG → RGB, written
+    top-left into a zeroed uint8 canvas, with the decoded size alongside.
+    ``ops.resize_crop_normalize(image, image_hw)`` does the reference's
+    Resize/CenterCrop/Normalize on the GPU from there.
+
+    An image larger than the canvas is first shrunk with PIL's
+    ``Image.reduce(k)`` (a k x k box average) for the smallest integer ``k``
+    that makes it fit — an approximation of resampling it at full size."""
+    import io
+
+    from PIL import Image
+
+    hc, wc = canvas_hw
+    out = np.zeros((len(pdf), hc, wc, 3), dtype=np.uint8)
+    hw = np.empty((len(pdf), 2), dtype=np.int32)
+    for i, b in enumerate(pdf["image"]):
+        with Image.open(io.BytesIO(b)) as im:
+            im = im.convert("RGB")
+            k = max(-(-im.height // hc), -(-im.width // wc))
+            if k > 1:
+                im = im.reduce(k)
+            a = np.asarray(im, dtype=np.uint8)
+        hw[i] = a.shape[:2]
+        out[i, :a.shape[0], :a.shape[1]] = a
+    return {"image": out, "image_hw": hw, "label": pdf["label"].to_numpy()}
+
+
 def decode_image_batch(pdf: pd.DataFrame, image_hw: Tuple[int, int] = (224, 224)) -> Dict[str, np.ndarray]:
     """Default transform for the synthetic image dataset: bytes → uint8
     NHWC array. Normalization/CHW happens on-device (fused HIP kernel) —

@@ -34,4 +34,5 @@ def require_ext() -> None:
         )
 
 
-from .preprocess import normalize_images  # noqa: E402,F401
+from .preprocess import (normalize_images,  # noqa: E402,F401
+                         resize_crop_geometry, resize_crop_normalize)

@@ -39,6 +39,132 @@ void normalize_u8_to_bf16(torch::Tensor in, torch::Tensor out,
       (long long)in.numel(), stream.stream());
 }
 
+extern "C" void launch_resize_crop_normalize(
+    const uint8_t* flat, long long flat_bytes, const int* desc, void* out,
+    const float* scale_dev, const float* shift_dev, int n, int crop,
+    const int* image_hw, int hc, int wc, int resize, hipStream_t stream);
+extern "C" int resize_crop_max_span_bytes();
+
+// What both resize_crop entry points ask of out, scale and shift.
+static void _check_resize_crop_out(const torch::Tensor& out, int64_t N,
+                                   int64_t crop, const torch::Tensor& scale,
+                                   const torch::Tensor& shift) {
+  TORCH_CHECK(crop >= 1 && crop <= 8192, "crop must be in [1, 8192]");
+  TORCH_CHECK(out.is_cuda() && out.scalar_type() == torch::kBFloat16 &&
+                  out.dim() == 4 && out.size(0) == N && out.size(1) == 3 &&
+                  out.size(2) == crop && out.size(3) == crop &&
+                  out.is_contiguous(at::MemoryFormat::ChannelsLast),
+              "out must be bf16 [N,3,crop,crop] channels_last on GPU");
+  TORCH_CHECK(scale.is_cuda() && shift.is_cuda() && scale.numel() == 3 &&
+                  shift.numel() == 3 &&
+                  scale.scalar_type() == torch::kFloat32 &&
+                  shift.scalar_type() == torch::kFloat32,
+              "scale/shift must be 3-element float32 device tensors");
+  TORCH_CHECK(N * ((crop + 7) / 8) < (int64_t(1) << 31),
+              "too many tiles for one grid");
+}
+
+// One h x w -> nh x nw image: the kernel's integer tap arithmetic stays in
+// int32, and one output column's taps (2 * support + 2 pixels) fit a row
+// buffer.
+static void _check_resize_crop_scale(int64_t i, int64_t h, int64_t w,
+                                     int64_t nh, int64_t nw) {
+  const int64_t two31 = int64_t(1) << 31;
+  TORCH_CHECK(2 * h * nh < two31 && 2 * w * nw < two31,
+              "image ", i, ": 2 * n_in * n_out must stay below 2^31");
+  TORCH_CHECK(3 * (2 * ((w + nw - 1) / nw) + 2) <=
+                  resize_crop_max_span_bytes(),
+              "image ", i, ": horizontal shrink factor too large");
+}
+
+// Fused resize + center crop + normalize (resize_crop.hip).
+// flat: uint8 [B], every source image somewhere inside it; desc: int32
+// [N,8] on the GPU, per image (byte offset, h, w, row pitch in bytes, nh, nw,
+// top, left); desc_cpu: the same values on the host, which is what gets
+// checked here, before any launch; out: bf16 [N,3,crop,crop] channels_last;
+// scale/shift as for normalize_u8_to_bf16.
+void resize_crop_normalize(torch::Tensor flat, torch::Tensor desc,
+                           torch::Tensor desc_cpu, torch::Tensor out,
+                           torch::Tensor scale, torch::Tensor shift,
+                           int64_t crop) {
+  TORCH_CHECK(flat.is_cuda() && flat.scalar_type() == torch::kUInt8 &&
+                  flat.dim() == 1 && flat.is_contiguous(),
+              "flat must be a contiguous 1-d uint8 GPU tensor");
+  TORCH_CHECK(flat.numel() < (int64_t(1) << 31),
+              "flat must hold fewer than 2^31 bytes (int32 offsets)");
+  TORCH_CHECK(desc.is_cuda() && desc.scalar_type() == torch::kInt32 &&
+                  desc.dim() == 2 && desc.size(1) == 8 &&
+                  desc.is_contiguous(),
+              "desc must be a contiguous int32 [N,8] GPU tensor");
+  TORCH_CHECK(!desc_cpu.is_cuda() &&
+                  desc_cpu.scalar_type() == torch::kInt32 &&
+                  desc_cpu.is_contiguous() &&
+                  desc_cpu.sizes() == desc.sizes(),
+              "desc_cpu must be the host copy of desc");
+  const int64_t N = desc.size(0);
+  _check_resize_crop_out(out, N, crop, scale, shift);
+  TORCH_CHECK(flat.device() == out.device() && desc.device() == out.device(),
+              "flat, desc and out must share a device");
+  const int* d = desc_cpu.data_ptr<int>();
+  for (int64_t i = 0; i < N; ++i, d += 8) {
+    const int64_t off = d[0], h = d[1], w = d[2], pitch = d[3], nh = d[4],
+                  nw = d[5], top = d[6], left = d[7];
+    TORCH_CHECK(h >= 1 && w >= 1 && off >= 0 && pitch >= 3 * w &&
+                    off + (h - 1) * pitch + 3 * w <= flat.numel(),
+                "image ", i, " (offset ", off, ", ", h, "x", w, ", pitch ",
+                pitch, ") leaves the ", flat.numel(), "-byte buffer");
+    TORCH_CHECK(nh >= crop && nw >= crop && top >= 0 && left >= 0 &&
+                    top + crop <= nh && left + crop <= nw,
+                "image ", i, ": crop window outside the resized image");
+    _check_resize_crop_scale(i, h, w, nh, nw);
+  }
+  if (N == 0) return;
+  launch_resize_crop_normalize(
+      flat.data_ptr<uint8_t>(), (long long)flat.numel(),
+      desc.data_ptr<int>(), out.data_ptr(), scale.data_ptr<float>(),
+      shift.data_ptr<float>(), (int)N, (int)crop, nullptr, 0, 0, 0,
+      at::cuda::getCurrentHIPStream().stream());
+  C10_HIP_KERNEL_LAUNCH_CHECK();
+}
+
+// The same from a padded canvas uint8 [N,Hc,Wc,3] whose image i fills the
+// top-left image_hw[i] = (h, w) corner. image_hw is int32 [N,2] on the GPU
+// and is read by the kernel alone, which clamps it into the canvas and
+// derives the resize/crop geometry itself: no host read, so the call can be
+// captured into a graph. What is checked here is therefore the worst case
+// the canvas admits, a 1-pixel short side against the full long side.
+void resize_crop_normalize_canvas(torch::Tensor canvas,
+                                  torch::Tensor image_hw, torch::Tensor out,
+                                  torch::Tensor scale, torch::Tensor shift,
+                                  int64_t resize, int64_t crop) {
+  TORCH_CHECK(canvas.is_cuda() && canvas.scalar_type() == torch::kUInt8 &&
+                  canvas.dim() == 4 && canvas.size(3) == 3 &&
+                  canvas.is_contiguous() && canvas.size(1) >= 1 &&
+                  canvas.size(2) >= 1,
+              "canvas must be a contiguous uint8 [N,Hc,Wc,3] GPU tensor");
+  TORCH_CHECK(canvas.numel() < (int64_t(1) << 31),
+              "canvas must hold fewer than 2^31 bytes");
+  const int64_t N = canvas.size(0), hc = canvas.size(1), wc = canvas.size(2);
+  TORCH_CHECK(image_hw.is_cuda() && image_hw.scalar_type() == torch::kInt32 &&
+                  image_hw.is_contiguous() && image_hw.dim() == 2 &&
+                  image_hw.size(0) == N && image_hw.size(1) == 2,
+              "image_hw must be a contiguous int32 [N,2] GPU tensor");
+  TORCH_CHECK(resize >= crop && resize <= 8192, "need crop <= resize <= 8192");
+  _check_resize_crop_out(out, N, crop, scale, shift);
+  TORCH_CHECK(canvas.device() == out.device() &&
+                  image_hw.device() == out.device(),
+              "canvas, image_hw and out must share a device");
+  _check_resize_crop_scale(0, hc, wc, resize * hc, resize);   // w = 1 ...
+  _check_resize_crop_scale(0, hc, wc, resize, resize * wc);   // ... or h = 1
+  if (N == 0) return;
+  launch_resize_crop_normalize(
+      canvas.data_ptr<uint8_t>(), (long long)canvas.numel(), nullptr,
+      out.data_ptr(), scale.data_ptr<float>(), shift.data_ptr<float>(),
+      (int)N, (int)crop, image_hw.data_ptr<int>(), (int)hc, (int)wc,
+      (int)resize, at::cuda::getCurrentHIPStream().stream());
+  C10_HIP_KERNEL_LAUNCH_CHECK();
+}
+
 extern "C" void launch_diff_center(const float* yT, float* wc, float* wm,
                                    int T, long long G, int S, int d,
                                    hipStream_t stream);
@@ -1034,6 +1160,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "fp32 element count of the stem weight-grad accumulation scratch");
   m.def("normalize_u8_to_bf16", &normalize_u8_to_bf16,
         "fused uint8 NHWC -> normalized bf16 (same memory order)");
+  m.def("resize_crop_normalize", &resize_crop_normalize,
+        "fused antialiased resize + center crop + normalize of ragged uint8 "
+        "HWC images -> bf16 [N,3,crop,crop] channels_last");
+  m.def("resize_crop_normalize_canvas", &resize_crop_normalize_canvas,
+        "the same from a padded canvas [N,Hc,Wc,3] and device-side image_hw; "
+        "geometry in the kernel, no host read (graph-capturable)");
   m.def("groupfit_eval", &groupfit_eval,
         "batched per-group ARIMAX candidate evaluation (validation MSE)");
   m.def("groupfit_final", &groupfit_final,

@@ -10,7 +10,9 @@ Endpoints:
   GET  /health                 -> {"status": "ok", "device": ...}
   POST /classify               -> top-k classes for a uint8 HWC image
                                   (json list) — runs the same fused
-                                  normalize + bf16 path as training
+                                  normalize + bf16 path as training;
+                                  with "resize" (and "crop") the fused
+                                  resize + center-crop + normalize kernel
   POST /forecast               -> per-group demand forecast: long-format
                                   records in, fitted values out (the W1
                                   GPU pipeline under the hood); with
@@ -31,6 +33,10 @@ except ImportError:  # pragma: no cover - pydantic ships with fastapi
 class ClassifyRequest(BaseModel):
     image: list  # HWC uint8 nested list
     top_k: int = 5
+    # the reference's inference transform, Resize(resize) -> CenterCrop(crop);
+    # unset: the image is fed at its own size
+    resize: Optional[int] = None
+    crop: int = 224
 
 
 class ForecastRequest(BaseModel):
@@ -64,12 +70,21 @@ def create_app(classifier=None, model_name: str = "resnet18",
         arr = np.asarray(req.image, dtype=np.uint8)
         if arr.ndim != 3 or arr.shape[-1] != 3:
             raise HTTPException(400, "image must be HWC uint8 with C=3")
+        if req.resize is not None and not 1 <= req.crop <= req.resize:
+            raise HTTPException(400, "need 1 <= crop <= resize")
         x = torch.from_numpy(arr).unsqueeze(0).to(dev)
         with torch.no_grad(), torch.autocast(
                 device_type="cuda", dtype=torch.bfloat16,
                 enabled=dev.type == "cuda"):
-            from .ops import normalize_images
-            xin = normalize_images(x)
+            from .ops import normalize_images, resize_crop_normalize
+            if req.resize is not None:
+                try:
+                    xin = resize_crop_normalize([x[0]], resize=req.resize,
+                                                crop=req.crop)
+                except ValueError as e:
+                    raise HTTPException(400, str(e))
+            else:
+                xin = normalize_images(x)
             if dev.type == "cpu":
                 xin = xin.float()
             logits = classifier(xin).float().softmax(-1)[0]

@@ -71,10 +71,16 @@ class ImageStreamDataModule(DataModule):
         stagers: int = 2,
         val_fraction_shards: bool = True,
         image_format: str = "raw",
+        device_resize: bool = False,
+        canvas_hw=(512, 512),
     ):
         if image_format not in ("raw", "jpeg"):
             raise ValueError("image_format must be 'raw' or 'jpeg'")
+        if device_resize and image_format != "jpeg":
+            raise ValueError("device_resize goes with image_format='jpeg'")
         self.image_format = image_format
+        self.device_resize = device_resize
+        self.canvas_hw = tuple(canvas_hw)
         self.data_dir = data_dir
         self.batch_size = batch_size
         self.workers_count = workers_count
@@ -103,7 +109,22 @@ class ImageStreamDataModule(DataModule):
     def _make_loader(self, num_epochs: Optional[int]):
         self.setup()
         h, w = self.image_hw
-        if self.image_format == "jpeg":
+        if self.image_format == "jpeg" and self.device_resize:
+            # decode only: images land on a fixed canvas with their size
+            # alongside, and resize + crop + normalize run on the device
+            # (ops.resize_crop_normalize, picked by ImageClassifier._unpack
+            # when the batch carries image_hw)
+            from functools import partial
+
+            from ..data.generator import decode_jpeg_canvas
+            hc, wc = self.canvas_hw
+            kwargs = dict(transform_spec=TransformSpec(
+                partial(decode_jpeg_canvas, canvas_hw=(hc, wc)),
+                edit_fields=[("image", np.uint8, (hc, wc, 3), False),
+                             ("image_hw", np.int32, (2,), False),
+                             ("label", np.int64, (), False)],
+                selected_fields=["image", "image_hw", "label"]))
+        elif self.image_format == "jpeg":
             # encoded-JPEG datasets: the reference's real per-row CPU
             # transform (decode + resize + crop) runs in the reader pool
             # (deep_learning/2...py:282-296); normalize stays on device

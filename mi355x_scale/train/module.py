@@ -80,7 +80,14 @@ class ImageClassifier(ScaleModule):
             x, y = batch
         if y.dim() > 1:
             y = y.reshape(-1)
-        if x.dtype == torch.uint8 and x.dim() == 4 and x.shape[-1] == 3:
+        if isinstance(batch, dict) and batch.get("image_hw") is not None:
+            # Decoded images of any size on a padded canvas (datamodule
+            # device_resize=True): fused resize + crop + normalize.
+            from ..ops import resize_crop_normalize
+            x = resize_crop_normalize(x, batch["image_hw"])
+            if x.device.type == "cpu":
+                x = x.to(torch.float32)
+        elif x.dtype == torch.uint8 and x.dim() == 4 and x.shape[-1] == 3:
             # Raw NHWC uint8 from the streaming loader: fused HIP
             # normalize (GPU) / torch reference (CPU) — ops.preprocess.
             from ..ops import normalize_images

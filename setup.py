@@ -16,6 +16,7 @@ from torch.utils.cpp_extension import (BuildExtension, CppExtension,
 SRC = [
     "mi355x_scale/ops/csrc/bindings.cpp",
     "mi355x_scale/ops/csrc/preprocess.hip",
+    "mi355x_scale/ops/csrc/resize_crop.hip",
     "mi355x_scale/ops/csrc/groupfit.hip",
     "mi355x_scale/ops/csrc/hwfit.hip",
     "mi355x_scale/ops/csrc/mfma_project.hip",
