@@ -17,6 +17,7 @@ from typing import List, Optional, Type, Union
 import torch
 import torch.nn as nn
 
+from ..ops.conv1x1 import Conv1x1
 from ..ops.conv3x3 import Conv3x3
 from ..ops.fused_bn import FusedBNReLU2d
 from ..ops.maxpool import MaxPool3x3s2
@@ -31,7 +32,21 @@ def _conv3x3(cin: int, cout: int, stride: int = 1) -> nn.Conv2d:
 
 
 def _conv1x1(cin: int, cout: int, stride: int = 1) -> nn.Conv2d:
+    if stride == 1:
+        # MFMA pointwise GEMM, opt-in (ops/csrc/conv1x1.hip)
+        return Conv1x1(cin, cout)
     return nn.Conv2d(cin, cout, 1, stride=stride, bias=False)
+
+
+def _conv_bn(conv: nn.Conv2d, bn: FusedBNReLU2d, x: torch.Tensor,
+             residual: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``bn(conv(x), residual)``. A pointwise conv on its HIP path has
+    already summed the BN's batch statistics in its epilogue, so the BN
+    skips its reduce pass over the conv's output."""
+    if bn.training and isinstance(conv, Conv1x1) and conv.stats_ok(x):
+        out, partial = conv.forward_with_stats(x)
+        return bn(out, residual=residual, partial=partial)
+    return bn(conv(x), residual=residual)
 
 
 def _join_twin(x: torch.Tensor) -> torch.Tensor:
@@ -83,9 +98,9 @@ class Bottleneck(nn.Module):
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         skip = _join_twin(x)
         identity = skip if self.downsample is None else self.downsample(skip)
-        out = self.bn1(self.conv1(x))
+        out = _conv_bn(self.conv1, self.bn1, x)
         out = self.bn2(self.conv2(out))
-        return self.bn3(self.conv3(out), residual=identity)
+        return _conv_bn(self.conv3, self.bn3, out, residual=identity)
 
 
 class ResNet(nn.Module):

@@ -1,0 +1,152 @@
+"""MFMA pointwise (1x1, stride 1) convolution, NHWC bf16.
+
+Two thirds of a Bottleneck network's convs are 1x1 (the reference trains
+torchvision resnet50, ``deep_learning/
+2.distributed-data-loading-petastorm.py:150``). In channels-last storage
+a stride-1 1x1 conv is the plain GEMM ``Y[M, Cout] = X[M, Cin] . W^T``
+(``M = N*H*W``) with both operands contiguous along the reduction axis.
+``ops/csrc/conv1x1.hip`` computes it on ``v_mfma_f32_16x16x32_bf16``
+(128 x 64 output tile per block, K-step 64, double-buffered swizzled LDS
+tiles), and its statistics variant sums the BN batch statistics of the
+bf16 values it stores into one partial slot per M-block:
+``forward_with_stats`` hands them to ``FusedBNReLU2d.forward(...,
+partial=...)``, which then skips ``bn_fwd_reduce`` and with it the second
+read of the conv's output map. The data-grad ``dX = dY . W`` runs on the
+same GEMM body; it reads the weight as it lies and transposes it on the
+way out of LDS (``ds_read_b64_tr_b16``), so there is no scratch copy of
+``W^T``. Weight-grad stays on MIOpen.
+
+STATUS (first reading, one benchmark run on MI355X at batch 212 —
+benchmarks/bench_conv1x1.py, table in BASELINE.md): numerics are pinned
+to fp64 references (tests/test_conv1x1.py). Forward + statistics beats
+MIOpen + ``bn_fwd_reduce`` on eight of the twelve ResNet-50 shapes and
+LOSES on four (512->128, 512->256, 1024->256, 1024->512, 6-23% slower);
+the plain forward loses to MIOpen on ten of twelve; the data-grad is
+ahead on ten and behind on 256->1024. The load phase is the bound at
+Cin >= 512 (NOTES_NEXT.md lead 9). ResNet-50 step with the switch on:
+9,231 vs 8,891 samples/s (two alternating runs each). Default-OFF:
+``MI355X_CONV1X1=1``, read on every call, opts in; a per-shape default
+needs three alternating runs per shape and re-baselines outputs.
+
+``Conv1x1`` subclasses ``nn.Conv2d`` (state-dict compatible, same init).
+When enabled, the HIP path takes CUDA bf16 channels-last inputs and a
+bf16 weight with Cin, Cout in {64, 128, ..., 2048}; everything else
+falls through to ``F.conv2d``.
+"""
+from __future__ import annotations
+
+import os
+
+import torch
+import torch.nn as nn
+import torch.nn.functional as F
+
+
+def _fwd(x: torch.Tensor, weight: torch.Tensor, stats: bool):
+    """Launch the forward GEMM. ``stats``: also fill the BN partial sums of
+    the output (fp32 ``[2*Cout][nblocks]``, the layout ``bn_fwd_finalize``
+    reads); otherwise ``partial`` is None."""
+    from . import _C
+    N, _, H, W = x.shape
+    cout = weight.shape[0]
+    out = torch.empty((N, cout, H, W), dtype=torch.bfloat16, device=x.device,
+                      memory_format=torch.channels_last)
+    partial = None
+    if stats:
+        partial = torch.empty(2 * cout * _C.conv1x1_fwd_blocks(N * H * W),
+                              dtype=torch.float32, device=x.device)
+    # the kernel addresses raw NHWC storage: hand the physical views over
+    _C.conv1x1_fwd(x.permute(0, 2, 3, 1), weight, out.permute(0, 2, 3, 1),
+                   partial)
+    return out, partial
+
+
+def _bwd(ctx, dy: torch.Tensor):
+    from . import _C
+    x, weight = ctx.saved_tensors
+    if dy.dtype != torch.bfloat16:
+        dy = dy.to(torch.bfloat16)
+    dy = dy.contiguous(memory_format=torch.channels_last)
+    dx = dw = None
+    if ctx.needs_input_grad[0]:
+        dx = torch.empty_like(x)
+        _C.conv1x1_dgrad(dy.permute(0, 2, 3, 1), weight,
+                         dx.permute(0, 2, 3, 1))
+    if ctx.needs_input_grad[1]:
+        dw = torch.ops.aten.convolution_backward(
+            dy, x, weight, None, [1, 1], [0, 0], [1, 1], False, [0, 0], 1,
+            [False, True, False])[1]
+    return dx, dw
+
+
+class _Conv1x1Fn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x: torch.Tensor, weight: torch.Tensor):
+        out, _ = _fwd(x, weight, False)
+        ctx.save_for_backward(x, weight)
+        return out
+
+    @staticmethod
+    def backward(ctx, dy: torch.Tensor):
+        return _bwd(ctx, dy)
+
+
+class _Conv1x1StatsFn(torch.autograd.Function):
+    """Forward conv that also returns the BN partial sums of its output
+    (non-differentiable); backward is ``_Conv1x1Fn``'s."""
+
+    @staticmethod
+    def forward(ctx, x: torch.Tensor, weight: torch.Tensor):
+        out, partial = _fwd(x, weight, True)
+        ctx.save_for_backward(x, weight)
+        ctx.mark_non_differentiable(partial)
+        # otherwise autograd hands backward a zero-filled tensor of
+        # partial's size every step
+        ctx.set_materialize_grads(False)
+        return out, partial
+
+    @staticmethod
+    def backward(ctx, dy, _dpartial):
+        if dy is None:
+            return None, None
+        return _bwd(ctx, dy)
+
+
+class Conv1x1(nn.Conv2d):
+    """1x1/s1 conv (no bias) with the MFMA HIP fast path."""
+
+    def __init__(self, cin: int, cout: int):
+        super().__init__(cin, cout, 1, stride=1, bias=False)
+
+    def _hip_ok(self, x: torch.Tensor) -> bool:
+        if os.environ.get("MI355X_CONV1X1", "0") != "1" or not x.is_cuda:
+            return False
+        from . import HAVE_EXT, require_ext
+        cin, cout = self.in_channels, self.out_channels
+        ok = (x.dim() == 4 and x.shape[1] == cin
+              and cin % 64 == 0 and cin <= 2048
+              and cout % 64 == 0 and cout <= 2048
+              and x.dtype == torch.bfloat16
+              and self.weight.dtype == torch.bfloat16
+              and x.is_contiguous(memory_format=torch.channels_last)
+              and self.weight.is_contiguous())
+        if ok and not HAVE_EXT:
+            require_ext()  # asked for, and missing: no silent fallback
+        return ok
+
+    def stats_ok(self, x: torch.Tensor) -> bool:
+        """True when ``forward_with_stats`` will run the fused kernel."""
+        return self._hip_ok(x)
+
+    def forward_with_stats(self, x: torch.Tensor):
+        """``(conv(x), partial)``: ``partial`` holds the per-block BN sums
+        of the output for ``FusedBNReLU2d.forward(..., partial=...)``, or
+        is None when the HIP path does not engage."""
+        if self.stats_ok(x):
+            return _Conv1x1StatsFn.apply(x, self.weight)
+        return self.forward(x), None
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        if self._hip_ok(x):
+            return _Conv1x1Fn.apply(x, self.weight)
+        return F.conv2d(x, self.weight, None, 1, 0)

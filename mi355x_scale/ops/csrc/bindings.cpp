@@ -5,6 +5,7 @@
 #include <ATen/hip/HIPContext.h>
 #include <c10/hip/HIPException.h>
 #include <hip/hip_runtime.h>
+#include <algorithm>
 #include <cstdint>
 #include <cstdlib>
 
@@ -1136,7 +1137,96 @@ int64_t conv3x3_wrw_nchunks(int64_t Nb, int64_t H, int64_t C,
   return conv3x3_wrw_chunks((int)Nb, (int)H, (int)C, (int)chunks);
 }
 
+// Pointwise (1x1 s1) conv as a GEMM over raw NHWC storage (conv1x1.hip).
+extern "C" int conv1x1_m_blocks(long long M);
+extern "C" void launch_conv1x1_fwd(const void* x, const void* w, void* out,
+                                   float* partial, long long M, int Cin,
+                                   int Cout, hipStream_t stream,
+                                   int phase_mask);
+extern "C" void launch_conv1x1_dgrad(const void* dy, const void* w, void* dx,
+                                     long long M, int Cin, int Cout,
+                                     hipStream_t stream, int phase_mask);
+
+int64_t conv1x1_fwd_blocks(int64_t M) { return conv1x1_m_blocks(M); }
+
+// Geometry both entry points share: an input-side map [..., Cin] and an
+// output-side map [..., Cout] with the same leading (N, H, W) dims, and
+// the [Cout, Cin(,1,1)] weight, all bf16 on the GPU and dense.
+struct _C1Geom { long long M; int Cin, Cout; };
+
+static _C1Geom _check_conv1x1(const torch::Tensor& xi, const torch::Tensor& w,
+                              const torch::Tensor& xo) {
+  for (const torch::Tensor* t : {&xi, &w, &xo})
+    TORCH_CHECK(t->is_cuda() && t->scalar_type() == torch::kBFloat16 &&
+                    t->is_contiguous() && t->device() == xi.device(),
+                "conv1x1: dense bf16 GPU tensors on one device");
+  TORCH_CHECK(xi.dim() >= 2 && xo.dim() == xi.dim() && w.dim() >= 2,
+              "conv1x1: NHWC maps and a [Cout, Cin] weight");
+  const int64_t Cin = xi.size(-1), Cout = xo.size(-1);
+  TORCH_CHECK(Cin % 64 == 0 && Cin >= 64 && Cin <= 2048 &&
+                  Cout % 64 == 0 && Cout >= 64 && Cout <= 2048,
+              "conv1x1: Cin and Cout must be multiples of 64 up to 2048");
+  TORCH_CHECK(w.size(0) == Cout && w.numel() == Cout * Cin,
+              "conv1x1: weight must be [Cout, Cin] (1x1, groups 1)");
+  const int64_t M = xi.numel() / Cin;
+  TORCH_CHECK(M > 0 && xo.numel() == M * Cout &&
+                  xi.sizes().slice(0, xi.dim() - 1) ==
+                      xo.sizes().slice(0, xo.dim() - 1),
+              "conv1x1: maps must share their leading dims (stride 1)");
+  TORCH_CHECK(M < (1LL << 31) - 128 &&
+                  conv1x1_fwd_blocks(M) * (std::max(Cin, Cout) / 64) <
+                      (1LL << 31),
+              "conv1x1: too many rows for one launch");
+  return {(long long)M, (int)Cin, (int)Cout};
+}
+
+// out [N,H,W,Cout] = x [N,H,W,Cin] . w[Cout,Cin]^T. With ``partial`` (fp32,
+// 2*Cout*conv1x1_fwd_blocks(M) elements) the kernel also leaves the
+// per-M-block BN channel sums of the values it stores there, in the
+// [2C][nblocks] layout bn_fwd_finalize reads.
+void conv1x1_fwd(torch::Tensor x, torch::Tensor w, torch::Tensor out,
+                 c10::optional<torch::Tensor> partial = c10::nullopt,
+                 int64_t phase_mask = 7) {
+  const _C1Geom g = _check_conv1x1(x, w, out);
+  float* partial_p = nullptr;
+  if (partial.has_value()) {
+    const torch::Tensor& p = *partial;
+    TORCH_CHECK(p.is_cuda() && p.scalar_type() == torch::kFloat32 &&
+                    p.is_contiguous() && p.device() == x.device() &&
+                    p.numel() == 2 * g.Cout * conv1x1_fwd_blocks(g.M),
+                "partial must be fp32 [2*Cout*conv1x1_fwd_blocks(M)]");
+    partial_p = p.data_ptr<float>();
+  }
+  launch_conv1x1_fwd(x.data_ptr(), w.data_ptr(), out.data_ptr(), partial_p,
+                     g.M, g.Cin, g.Cout,
+                     at::cuda::getCurrentHIPStream().stream(),
+                     (int)phase_mask);
+}
+
+// dx [N,H,W,Cin] = dy [N,H,W,Cout] . w[Cout,Cin]. The kernel reads the
+// weight as it lies and transposes it on the way out of LDS, so there is
+// no scratch copy of w^T.
+void conv1x1_dgrad(torch::Tensor dy, torch::Tensor w, torch::Tensor dx,
+                   int64_t phase_mask = 7) {
+  const _C1Geom g = _check_conv1x1(dx, w, dy);
+  launch_conv1x1_dgrad(dy.data_ptr(), w.data_ptr(), dx.data_ptr(), g.M,
+                       g.Cin, g.Cout,
+                       at::cuda::getCurrentHIPStream().stream(),
+                       (int)phase_mask);
+}
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
+  m.def("conv1x1_fwd", &conv1x1_fwd,
+        "MFMA pointwise conv fwd (NHWC bf16), optional BN partial sums",
+        pybind11::arg("x"), pybind11::arg("w"), pybind11::arg("out"),
+        pybind11::arg("partial") = pybind11::none(),
+        pybind11::arg("phase_mask") = 7);
+  m.def("conv1x1_fwd_blocks", &conv1x1_fwd_blocks,
+        "M-block (= BN partial slot) count of the pointwise conv fwd");
+  m.def("conv1x1_dgrad", &conv1x1_dgrad,
+        "MFMA pointwise conv data-grad (NHWC bf16)",
+        pybind11::arg("dy"), pybind11::arg("w"), pybind11::arg("dx"),
+        pybind11::arg("phase_mask") = 7);
   m.def("conv3x3_wrw", &conv3x3_wrw,
         "MFMA 3x3/s1 CxC weight grad (fp32 accum, bf16 cast to view)",
         pybind11::arg("x"), pybind11::arg("dy"), pybind11::arg("part"),

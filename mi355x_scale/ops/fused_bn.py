@@ -36,6 +36,9 @@ Passes and kernels the HIP path leaves out:
   rebuilds the un-pooled gradient in registers from the pooled gradient
   and the u8 window codes (``bn_pool_bwd_*``);
   ``MI355X_BN_POOL_FUSED_BWD=0`` selects the three-kernel path for A/B.
+* ``forward(x, partial=...)`` takes the same kind of per-block sums from
+  a pointwise conv's epilogue (``Conv1x1.forward_with_stats``, opt-in)
+  and skips ``bn_fwd_reduce`` in the same way.
 * ``bn_fwd_finalize`` bumps ``num_batches_tracked`` on the device, so no
   per-BN ``+= 1`` kernel runs; inside hipGraph capture ``bn_bwd_finalize``
   accumulates straight into the flat grad views (``MI355X_BN_FUSED_ACC``).
@@ -95,13 +98,17 @@ def _channel_grads(weight, bias, C, dev):
 class _FusedBNFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, residual, weight, bias, running_mean, running_var,
-                momentum, eps, relu, num_batches_tracked, join=False):
+                momentum, eps, relu, num_batches_tracked, join=False,
+                partial=None):
         C = x.shape[1]
         rows = x.numel() // C
         dev = x.device
         mean = torch.empty(C, dtype=torch.float32, device=dev)
         invstd = torch.empty(C, dtype=torch.float32, device=dev)
-        partial = _C.bn_fwd_reduce(x, C)
+        # a ready-made partial (the epilogue sums of the conv that wrote
+        # x, same [2C][nblocks] layout) replaces the full read of x
+        if partial is None:
+            partial = _C.bn_fwd_reduce(x, C)
         # the finalize kernel also bumps the step counter when given one
         _C.bn_fwd_finalize(partial, mean, invstd, running_mean, running_var,
                            momentum, eps, rows, C, True, num_batches_tracked)
@@ -132,7 +139,7 @@ class _FusedBNFn(torch.autograd.Function):
         if dz is None:
             dz, dz2 = dz2, None
         if dz is None:  # joined forward, neither output used
-            return (None,) * 11
+            return (None,) * 12
         if not dz.is_contiguous(memory_format=torch.channels_last):
             dz = dz.contiguous(memory_format=torch.channels_last)
         if (dz2 is not None and
@@ -182,7 +189,7 @@ class _FusedBNFn(torch.autograd.Function):
         if fuse_acc:  # the kernel already accumulated the channel grads
             dweight = dbias = None
         return (dx, dym, dweight, dbias, None, None, None, None, None, None,
-                None)
+                None, None)
 
 
 class _FusedBNPoolFn(torch.autograd.Function):
@@ -318,7 +325,12 @@ class FusedBNReLU2d(nn.Module):
         return F.max_pool2d(self.forward(x), 3, stride=2, padding=1)
 
     def forward(self, x: torch.Tensor,
-                residual: Optional[torch.Tensor] = None) -> torch.Tensor:
+                residual: Optional[torch.Tensor] = None,
+                partial: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """``partial``: per-block channel sums of ``x`` already produced by
+        the kernel that wrote it (``Conv1x1.forward_with_stats``); in
+        training mode on the HIP path the reduce pass over ``x`` is then
+        skipped, and it is ignored everywhere else."""
         if _hip_supported(x):
             require_ext()  # GPU bf16 path never falls back silently
             x = x.contiguous(memory_format=torch.channels_last)
@@ -332,7 +344,7 @@ class FusedBNReLU2d(nn.Module):
                 out = _FusedBNFn.apply(
                     x, residual, self.weight, self.bias, self.running_mean,
                     self.running_var, self.momentum, self.eps, self.relu,
-                    self.num_batches_tracked, join)
+                    self.num_batches_tracked, join, partial)
                 if not join:
                     return out
                 # Residual layer = a block's output, which the next block
