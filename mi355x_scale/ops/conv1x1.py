@@ -14,7 +14,27 @@ partial=...)``, which then skips ``bn_fwd_reduce`` and with it the second
 read of the conv's output map. The data-grad ``dX = dY . W`` runs on the
 same GEMM body; it reads the weight as it lies and transposes it on the
 way out of LDS (``ds_read_b64_tr_b16``), so there is no scratch copy of
-``W^T``. Weight-grad stays on MIOpen.
+``W^T``.
+
+The weight-grad ``dW = dY^T . X`` contracts over M, the strided index of
+both maps, into a tiny output. ``conv1x1_wrw_kernel`` splits M into chunks
+(about two blocks per CU), stages 32-row tiles as they lie, feeds both
+MFMA operands with transposed LDS reads and writes one fp32 partial per
+chunk; ``conv1x1_wrw_reduce_kernel`` sums them in a fixed order and
+rounds once to bf16. It is a second opt-in, ``MI355X_CONV1X1_WRW=1``
+(default ``0``, read on every call, effective only where
+``MI355X_CONV1X1=1`` engages the HIP path); with it off the weight-grad is
+MIOpen's. While a graph is being captured and ``weight.grad`` is a bf16
+tensor of the weight's shape, dense like the weight (the FlatAdam views), the
+reduce kernel ADDS into that view, bit for bit what ``AccumulateGrad``'s
+bf16 add of a returned ``dw`` produces, and backward returns ``None`` for
+the weight: the per-weight add launch is gone. Like the fused BN's
+in-place channel grads this assumes the capture is of a ``.backward()``
+into ``.grad``: tensor hooks on the weight do not see that gradient, and
+``torch.autograd.grad(...)`` called INSIDE a capture with such a
+``.grad`` present would get None for the weight and find ``.grad``
+added to (keep the second switch off for that). Everywhere else
+backward returns a fresh ``dw``.
 
 STATUS (first reading, one benchmark run on MI355X at batch 212 —
 benchmarks/bench_conv1x1.py, table in BASELINE.md): numerics are pinned
@@ -27,6 +47,16 @@ Cin >= 512 (NOTES_NEXT.md lead 9). ResNet-50 step with the switch on:
 9,231 vs 8,891 samples/s (two alternating runs each). Default-OFF:
 ``MI355X_CONV1X1=1``, read on every call, opts in; a per-shape default
 needs three alternating runs per shape and re-baselines outputs.
+Weight-grad: pinned to fp64 (tests/test_conv1x1_wrw.py); the twelve-shape
+table against MIOpen + the grad add and the ResNet-50 step with the
+second switch on are in BASELINE.md. At batch 212
+(three runs) it is faster than MIOpen + the grad add on eight of the
+twelve shapes and level on 64->256, 256->64, 256->128 and 512->256; the
+ResNet-50 step goes 22.89 -> 22.80 ms with the second switch on (three
+alternating runs each, slowest new above fastest old). The H = 56
+shapes are HBM-bound (operands at 4.9-5.7 TB/s of 8); from H = 28 down
+the bound is the tiles' re-reads through L2 and/or load latency
+(BASELINE.md has the byte counts). Default-OFF as well.
 
 ``Conv1x1`` subclasses ``nn.Conv2d`` (state-dict compatible, same init).
 When enabled, the HIP path takes CUDA bf16 channels-last inputs and a
@@ -73,10 +103,36 @@ def _bwd(ctx, dy: torch.Tensor):
         _C.conv1x1_dgrad(dy.permute(0, 2, 3, 1), weight,
                          dx.permute(0, 2, 3, 1))
     if ctx.needs_input_grad[1]:
-        dw = torch.ops.aten.convolution_backward(
-            dy, x, weight, None, [1, 1], [0, 0], [1, 1], False, [0, 0], 1,
-            [False, True, False])[1]
+        if os.environ.get("MI355X_CONV1X1_WRW", "0") == "1":
+            dw = _wrw(x, dy, weight)
+        else:
+            dw = torch.ops.aten.convolution_backward(
+                dy, x, weight, None, [1, 1], [0, 0], [1, 1], False, [0, 0],
+                1, [False, True, False])[1]
     return dx, dw
+
+
+def _wrw(x: torch.Tensor, dy: torch.Tensor, weight: torch.Tensor):
+    """Weight-grad on the HIP kernels. Returns a fresh ``dw``, or None after
+    adding it into ``weight.grad`` in place (under graph capture, when the
+    grad is a dense bf16 tensor of the weight's shape; the weight is dense
+    wherever the HIP path engages, so the two share one layout)."""
+    from . import _C
+    N, cin, H, W = x.shape
+    cout = weight.shape[0]
+    with torch.cuda.device(x.device):  # the chunk rule asks this device
+        nch = _C.conv1x1_wrw_nchunks(N * H * W, cin, cout)
+    part = torch.empty(nch * cout * cin, dtype=torch.float32, device=x.device)
+    xn, dyn = x.permute(0, 2, 3, 1), dy.permute(0, 2, 3, 1)
+    g = weight.grad
+    if (torch.cuda.is_current_stream_capturing() and g is not None
+            and g.dtype == torch.bfloat16 and g.device == weight.device
+            and g.shape == weight.shape and g.is_contiguous()):
+        _C.conv1x1_wrw(xn, dyn, part, g, True)
+        return None
+    dw = torch.empty_like(weight)
+    _C.conv1x1_wrw(xn, dyn, part, dw)
+    return dw
 
 
 class _Conv1x1Fn(torch.autograd.Function):

@@ -1215,7 +1215,64 @@ void conv1x1_dgrad(torch::Tensor dy, torch::Tensor w, torch::Tensor dx,
                        (int)phase_mask);
 }
 
+extern "C" int conv1x1_wrw_chunks(long long M, int Cin, int Cout, int req);
+extern "C" void launch_conv1x1_wrw(const void* x, const void* dy, float* part,
+                                   void* dw, long long M, int Cin, int Cout,
+                                   int nchunks, int accumulate,
+                                   hipStream_t stream, int phase_mask);
+
+// Chunk count the weight-grad uses for ``chunks`` (0 = the default rule,
+// which depends on the CU count of the CURRENT device):
+// ``part`` holds exactly that many [Cout][Cin] fp32 slices.
+int64_t conv1x1_wrw_nchunks(int64_t M, int64_t Cin, int64_t Cout,
+                            int64_t chunks = 0) {
+  TORCH_CHECK(M > 0 && M < (1LL << 31) - 128 && chunks >= 0 &&
+                  chunks < (1LL << 31) && Cin % 64 == 0 && Cin >= 64 &&
+                  Cin <= 2048 && Cout % 64 == 0 && Cout >= 64 && Cout <= 2048,
+              "conv1x1_wrw: M, chunks or channel counts out of range");
+  const int n = conv1x1_wrw_chunks(M, (int)Cin, (int)Cout, (int)chunks);
+  TORCH_CHECK(n > 0, "conv1x1_wrw: cannot read the device's CU count");
+  return n;
+}
+
+// dw [Cout, Cin(,1,1)] = dy [N,H,W,Cout]^T . x [N,H,W,Cin], split over M
+// into conv1x1_wrw_nchunks(...) fp32 partials in ``part`` (every element
+// is written: torch.empty serves) and reduced in a second launch that
+// rounds once to bf16. ``accumulate``: add that rounded value into the
+// bf16 values ``dw`` holds, as a bf16 tensor add would (dw may be a flat
+// grad view).
+void conv1x1_wrw(torch::Tensor x, torch::Tensor dy, torch::Tensor part,
+                 torch::Tensor dw, bool accumulate = false,
+                 int64_t chunks = 0, int64_t phase_mask = 7) {
+  const _C1Geom g = _check_conv1x1(x, dw, dy);
+  // the default chunk rule reads the CU count of the current device
+  const c10::DeviceGuard guard(x.device());
+  const int64_t nch = conv1x1_wrw_nchunks(g.M, g.Cin, g.Cout, chunks);
+  TORCH_CHECK(part.is_cuda() && part.scalar_type() == torch::kFloat32 &&
+                  part.is_contiguous() && part.device() == x.device() &&
+                  part.numel() == nch * g.Cout * g.Cin,
+              "part must be fp32 [conv1x1_wrw_nchunks*Cout*Cin] (", nch,
+              " chunks)");
+  TORCH_CHECK(nch * (g.Cin / 64) * (g.Cout / 64) < (1LL << 31),
+              "conv1x1_wrw: too many blocks for one launch");
+  launch_conv1x1_wrw(x.data_ptr(), dy.data_ptr(), part.data_ptr<float>(),
+                     dw.data_ptr(), g.M, g.Cin, g.Cout, (int)nch,
+                     accumulate ? 1 : 0,
+                     at::cuda::getCurrentHIPStream().stream(),
+                     (int)phase_mask);
+}
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
+  m.def("conv1x1_wrw", &conv1x1_wrw,
+        "MFMA pointwise conv weight-grad (split over M, fp32 partials, "
+        "bf16 store or accumulate into dw)",
+        pybind11::arg("x"), pybind11::arg("dy"), pybind11::arg("part"),
+        pybind11::arg("dw"), pybind11::arg("accumulate") = false,
+        pybind11::arg("chunks") = 0, pybind11::arg("phase_mask") = 7);
+  m.def("conv1x1_wrw_nchunks", &conv1x1_wrw_nchunks,
+        "chunk (= fp32 partial slice) count of the pointwise weight-grad",
+        pybind11::arg("M"), pybind11::arg("Cin"), pybind11::arg("Cout"),
+        pybind11::arg("chunks") = 0);
   m.def("conv1x1_fwd", &conv1x1_fwd,
         "MFMA pointwise conv fwd (NHWC bf16), optional BN partial sums",
         pybind11::arg("x"), pybind11::arg("w"), pybind11::arg("out"),

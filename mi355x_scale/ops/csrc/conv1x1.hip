@@ -1,6 +1,6 @@
 // Hand-written MFMA pointwise (1x1, stride 1) convolution for gfx950,
 // NHWC bf16: forward, forward with BatchNorm statistics in the epilogue,
-// and data-grad. Weight-grad stays on MIOpen.
+// data-grad, and (second half of this file) a split-K weight-grad.
 //
 // Why: two thirds of a Bottleneck network's convs are 1x1 (the reference
 // trains torchvision resnet50, deep_learning/
@@ -302,4 +302,307 @@ extern "C" void launch_conv1x1_dgrad(const void* dy, const void* w, void* dx,
   hipLaunchKernelGGL(conv1x1_gemm_kernel<C1_DGRAD>, grid, block, 0, stream,
                      (const bf16*)dy, (const bf16*)w, (bf16*)dx,
                      (float*)nullptr, (int)M, Cin, Cout, ntn, phase_mask);
+}
+
+// ---------------------------------------------------------------------
+// Weight-grad:  dW[Cout][Cin] = sum_m dY[m][Cout] * X[m][Cin]   (m < M)
+//
+// The opposite of the GEMM above: the output is tiny (64x64 .. 2048x512),
+// the reduction runs over M (up to 665k at batch 212), and M is the
+// STRIDED index of both operands. So it has its own work split and its
+// own operand path:
+//   * work split: 256 threads own a TCO x TCI tile of dW and one chunk of
+//     M (split-K). A side is 128 wide when its channel count is a multiple
+//     of 128 and 64 otherwise (64, 192, 320, ...): four instantiations.
+//     The four waves sit 2 x 2, a wave holds (TCI/32) x (TCO/32)
+//     accumulator tiles (4 x 4 = 64 VGPRs at 128 x 128). blockIdx.x =
+//     chunk * tiles + tile: the tiles of one chunk are neighbours in
+//     launch order, so a chunk's rows come from HBM once and from L2 for
+//     the other tiles.
+//   * the MFMA computes dW^T: A = X^T (row = ci), B = dY (col = co). A
+//     lane then holds four consecutive ci of one co, which is 16
+//     contiguous bytes of part[chunk][co][ci]: the epilogue is plain
+//     16-byte stores, no transpose through LDS. Every partial slot is
+//     written by exactly one block; no atomics, bit-reproducible.
+//   * K-step WK = 32 rows of m. Tiles are [WK][64-channel] panels staged
+//     exactly as they lie in memory (16-byte loads along the channel axis,
+//     rows at or beyond M load zeros), global -> registers -> LDS,
+//     double-buffered, one barrier per step as in the GEMM body. WK = 32
+//     and not 64: two buffers of a 128 + 128 tile are 32 KB (64 KB at 64,
+//     which caps a CU at two blocks), and the staging registers are 16
+//     instead of 32 next to 64 accumulators and 32 operand registers: the
+//     128 x 128 instantiation compiles to 126 VGPRs, no scratch, which is
+//     under the 128 that FOUR blocks per CU need (the issue budgeted 168
+//     for three), so the launch bound pins four.
+//   * both operands come out of LDS with ds_read_b64_tr_b16, the C1_DGRAD
+//     B pattern: 16 lanes hand in four rows of 16 columns, two reads make
+//     one operand with k = 8*(lane>>4) + 4t + i for A and B alike. EXEC is
+//     all ones at every transposed read; the M tail is masked at the
+//     global loads only.
+//   * bank reasoning (not measured): a panel row is 128 bytes. One
+//     transposed read touches rows 8g + 4t + q (g = lane>>4, q = 0..3), 32
+//     bytes (one pair of 16-byte chunks) in each. With swz() the swizzle
+//     term of those rows is 4t + q: q and q^1 only swap the two chunks of
+//     one pair, and g does not enter, so the four rows of a 16-lane group
+//     fall on two chunk pairs and the four groups on the same banks. wswz()
+//     XORs the pair index with (row & 3) ^ (row>>3 & 1) and the chunk
+//     inside the pair with (row>>2 & 1): the four rows of a group take the
+//     four different pairs (a full 128 bytes, conflict-free if the LDS
+//     serves 16 lanes per pass over 32 banks), and groups g, g^1 take
+//     opposite pairs on rows of equal parity (conflict-free if it serves
+//     32 lanes per pass over 64 banks, where odd rows sit in the upper
+//     half). The 16-byte staging stores write whole rows, any chunk
+//     permutation of which is conflict-free.
+//
+// conv1x1_wrw_reduce_kernel sums the chunk partials in fp32, rounds once
+// to bf16 and stores, or adds into the bf16 values already there exactly
+// as a bf16 tensor add of the rounded result would (accumulate mode: the
+// kernel writes the flat grad view and AccumulateGrad has nothing to do).
+// With few chunks one thread walks them in index order. With many (tiny
+// dW, hundreds of chunks) that walk is one memory latency per batch on a
+// handful of blocks, so `groups` threads share an element: each sums a
+// contiguous run of chunks in index order, and the runs are added in
+// index order through LDS. Fixed order either way.
+#define WK 32                   // rows of m per K-step
+#define WPANEL (WK * 64)        // elements of one [WK][64] panel
+#define WRW_MIN_STEPS 4         // shortest chunk the default rule makes
+
+__device__ __forceinline__ int wswz(int row, int ch) {
+  const int f = (((row & 3) ^ ((row >> 3) & 1)) << 1) | ((row >> 2) & 1);
+  return row * 64 + ((ch ^ f) << 3);
+}
+
+// part[chunk][Cout][Cin] = sum over the chunk's rows. grid = chunks *
+// tiles; spc = K-steps per chunk (the last chunk may be shorter, never
+// empty). phase_mask: 1 = global loads + LDS staging, 4 = MFMA, 2 = epilogue.
+template <int TCO, int TCI>
+__global__ __launch_bounds__(256, 4) void conv1x1_wrw_kernel(
+    const bf16* __restrict__ X, const bf16* __restrict__ dY,
+    float* __restrict__ part, int M, int Cin, int Cout, int ntci, int tiles,
+    int spc, int phase_mask) {
+  constexpr int PI = TCI / 64, PO = TCO / 64;  // panels per operand
+  constexpr int IT = TCI / 32, OT = TCO / 32;  // accumulator tiles per wave
+  constexpr int TILE = (PI + PO) * WPANEL;     // one buffer: X panels, dY panels
+  __shared__ __attribute__((aligned(16))) bf16 smem[2 * TILE];
+  const int tid = threadIdx.x;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int lane = tid & 63;
+  const int l16 = lane & 15;
+  const int kgrp = lane >> 4;
+  const int chunk = blockIdx.x / tiles;
+  const int tile = blockIdx.x - chunk * tiles;
+  const int to = tile / ntci;
+  const int co0 = to * TCO, ci0 = (tile - to * ntci) * TCI;
+  const int s0 = chunk * spc;
+  const int ns = min(spc, (M + WK - 1) / WK - s0);
+
+  // staging: thread -> 16-byte chunk (tid & 7) of panel row (tid >> 3);
+  // 256 threads cover one panel, eight neighbours one 128-byte row
+  const int srow = tid >> 3, sch = tid & 7;
+  const int sto = wswz(srow, sch);
+  const int mrow = s0 * WK + srow;
+  const bf16* px = X + (long long)mrow * Cin + ci0 + sch * 8;
+  const bf16* py = dY + (long long)mrow * Cout + co0 + sch * 8;
+  const bf16x8 zv = {(bf16)0.0f, (bf16)0.0f, (bf16)0.0f, (bf16)0.0f,
+                     (bf16)0.0f, (bf16)0.0f, (bf16)0.0f, (bf16)0.0f};
+
+  // transposed read t takes rows 8*kgrp + 4t + q, columns 4p..4p+3 of
+  // column tile c: chunk 2c + (p >> 1), swizzled by wswz's term of that row
+  const int q = l16 >> 2, p = l16 & 3;
+  const int fq = (q ^ (kgrp & 1)) << 1;
+  const int tro0 = (8 * kgrp + q) * 64 + (p & 1) * 4;
+  const int tro1 = tro0 + 4 * 64;
+  const int trs0 = ((p >> 1) ^ fq) << 3;
+  const int trs1 = ((p >> 1) ^ (fq | 1)) << 3;
+  // first channel of the wave's quarter inside the block tile
+  const int wci = (wave & 1) * (TCI / 2), wco = (wave >> 1) * (TCO / 2);
+
+  f32x4 acc[IT][OT];
+#pragma unroll
+  for (int i = 0; i < IT; ++i)
+#pragma unroll
+    for (int j = 0; j < OT; ++j) acc[i][j] = (f32x4)0.0f;
+
+  bf16x8 rx[PI], ry[PO];
+
+#define W_GLOAD(ks)                                                         \
+  {                                                                         \
+    const bool alive = mrow + (ks) * WK < M;                                \
+    _Pragma("unroll") for (int u = 0; u < PI; ++u)                          \
+      rx[u] = alive ? *reinterpret_cast<const bf16x8*>(                     \
+                          px + (long long)(ks) * WK * Cin + u * 64)         \
+                    : zv;                                                   \
+    _Pragma("unroll") for (int u = 0; u < PO; ++u)                          \
+      ry[u] = alive ? *reinterpret_cast<const bf16x8*>(                     \
+                          py + (long long)(ks) * WK * Cout + u * 64)        \
+                    : zv;                                                   \
+  }
+#define W_LSTORE(buf)                                                       \
+  {                                                                         \
+    _Pragma("unroll") for (int u = 0; u < PI; ++u)                          \
+      *reinterpret_cast<bf16x8*>(smem + (buf) * TILE + u * WPANEL + sto) =  \
+          rx[u];                                                            \
+    _Pragma("unroll") for (int u = 0; u < PO; ++u)                          \
+      *reinterpret_cast<bf16x8*>(smem + (buf) * TILE + (PI + u) * WPANEL +  \
+                                 sto) = ry[u];                              \
+  }
+
+  if (phase_mask & 1) {
+    W_GLOAD(0)
+    W_LSTORE(0)
+  }
+  __syncthreads();
+
+#pragma unroll 1
+  for (int ks = 0; ks < ns; ++ks) {
+    const int buf = ks & 1;
+    const bool more = ks + 1 < ns;
+    if (more && (phase_mask & 1)) W_GLOAD(ks + 1)
+    if (phase_mask & 4) {
+      const bf16* xs = smem + buf * TILE;
+      const bf16* ys = xs + PI * WPANEL;
+      bf16x8 xf[IT], yf[OT];
+#pragma unroll
+      for (int i = 0; i < IT; ++i) {
+        const int col = wci + i * 16;  // panel col >> 6, column tile (col >> 4) & 3
+        const bf16* pn = xs + (col >> 6) * WPANEL;
+        xf[i] = tr_frag(pn + tro0 + ((col & 48) ^ trs0),
+                        pn + tro1 + ((col & 48) ^ trs1));
+      }
+#pragma unroll
+      for (int j = 0; j < OT; ++j) {
+        const int col = wco + j * 16;
+        const bf16* pn = ys + (col >> 6) * WPANEL;
+        yf[j] = tr_frag(pn + tro0 + ((col & 48) ^ trs0),
+                        pn + tro1 + ((col & 48) ^ trs1));
+      }
+#pragma unroll
+      for (int i = 0; i < IT; ++i)
+#pragma unroll
+        for (int j = 0; j < OT; ++j)
+          acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+              xf[i], yf[j], acc[i][j], 0, 0, 0);
+    }
+    if (more && (phase_mask & 1)) W_LSTORE(buf ^ 1)
+    __syncthreads();  // step ks is read, step ks+1 is in place
+  }
+#undef W_GLOAD
+#undef W_LSTORE
+  if (!(phase_mask & 2)) return;
+
+  // D row = 4*(lane>>4) + r is ci, D col = lane&15 is co: the four
+  // registers of a tile are 16 contiguous bytes of part[chunk][co][...]
+  float* const my = part + ((long long)chunk * Cout + co0 + wco + l16) * Cin +
+                    ci0 + wci + 4 * kgrp;
+#pragma unroll
+  for (int i = 0; i < IT; ++i)
+#pragma unroll
+    for (int j = 0; j < OT; ++j)
+      *reinterpret_cast<f32x4*>(my + (long long)j * 16 * Cin + i * 16) =
+          acc[i][j];
+}
+
+// dw[e] = bf16(sum_c part[c][e]), or in accumulate mode
+// bf16(float(dw[e]) + float(bf16(sum))). 256 threads = groups x (256 /
+// groups) 16-byte columns; grid = nel / (4 * (256 / groups)); nel is a
+// multiple of 4096 and groups a power of two <= 16, so nothing is ragged.
+__global__ __launch_bounds__(256) void conv1x1_wrw_reduce_kernel(
+    const float* __restrict__ part, bf16* __restrict__ dw, long long nel,
+    int chunks, int groups, int accumulate) {
+  __shared__ f32x4 red[256];
+  const int tid = threadIdx.x;
+  const int cols = 256 / groups;
+  const int g = tid / cols, col = tid - g * cols;
+  const long long e0 = ((long long)blockIdx.x * cols + col) * 4;
+  const int per = (chunks + groups - 1) / groups;
+  int c = g * per;
+  const int c1 = min(chunks, c + per);
+  const float* p = part + e0;
+  f32x4 s = (f32x4)0.0f;
+  // eight 16-byte loads in flight, added in chunk order
+  for (; c + 8 <= c1; c += 8) {
+    f32x4 v[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u)
+      v[u] = *reinterpret_cast<const f32x4*>(p + (long long)(c + u) * nel);
+#pragma unroll
+    for (int u = 0; u < 8; ++u) s += v[u];
+  }
+  for (; c < c1; ++c)
+    s += *reinterpret_cast<const f32x4*>(p + (long long)c * nel);
+  if (groups > 1) {
+    red[tid] = s;
+    __syncthreads();
+    if (g != 0) return;
+    for (int k = 1; k < groups; ++k) s += red[k * cols + col];
+  }
+  typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
+  bf16x4 o;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) o[e] = (bf16)s[e];
+  if (accumulate) {
+    const bf16x4 old = *reinterpret_cast<const bf16x4*>(dw + e0);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) o[e] = (bf16)((float)old[e] + (float)o[e]);
+  }
+  *reinterpret_cast<bf16x4*>(dw + e0) = o;
+}
+
+static int wrw_side(int c) { return c % 128 == 0 ? 128 : 64; }
+
+static int wrw_tiles(int Cin, int Cout) {
+  return (Cin / wrw_side(Cin)) * (Cout / wrw_side(Cout));
+}
+
+// Chunk count for a request. req > 0 forces it (clamped to the K-steps);
+// req == 0 takes the smallest count that puts about two blocks on every
+// CU of the current device, with chunks of at least WRW_MIN_STEPS
+// K-steps. Chunks are whole K-steps long and the value returned is the
+// effective count ceil(steps / steps_per_chunk): no chunk is empty.
+extern "C" int conv1x1_wrw_chunks(long long M, int Cin, int Cout, int req) {
+  const long long steps = (M + WK - 1) / WK;
+  long long n = req;
+  if (req <= 0) {
+    int dev = 0, cus = 0;  // of the current device: callers set it
+    if (hipGetDevice(&dev) != hipSuccess ||
+        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount,
+                              dev) != hipSuccess || cus <= 0)
+      return -1;
+    const int tiles = wrw_tiles(Cin, Cout);
+    n = (2 * cus + tiles - 1) / tiles;
+    if (n > steps / WRW_MIN_STEPS) n = steps / WRW_MIN_STEPS;
+  }
+  if (n > steps) n = steps;
+  if (n < 1) n = 1;
+  const long long spc = (steps + n - 1) / n;
+  return (int)((steps + spc - 1) / spc);
+}
+
+// ``nchunks`` is a value conv1x1_wrw_chunks returned; part holds
+// nchunks * Cout * Cin floats, every one of which is written.
+extern "C" void launch_conv1x1_wrw(const void* x, const void* dy, float* part,
+                                   void* dw, long long M, int Cin, int Cout,
+                                   int nchunks, int accumulate,
+                                   hipStream_t stream, int phase_mask) {
+  const int tci = wrw_side(Cin), tco = wrw_side(Cout);
+  const int ntci = Cin / tci, tiles = wrw_tiles(Cin, Cout);
+  const long long steps = (M + WK - 1) / WK;
+  const int spc = (int)((steps + nchunks - 1) / nchunks);
+  const dim3 grid(nchunks * tiles), block(256);
+#define W_LAUNCH(TCO, TCI)                                                  \
+  hipLaunchKernelGGL((conv1x1_wrw_kernel<TCO, TCI>), grid, block, 0,        \
+                     stream, (const bf16*)x, (const bf16*)dy, part, (int)M, \
+                     Cin, Cout, ntci, tiles, spc, phase_mask)
+  if (tco == 128 && tci == 128) W_LAUNCH(128, 128);
+  else if (tco == 128) W_LAUNCH(128, 64);
+  else if (tci == 128) W_LAUNCH(64, 128);
+  else W_LAUNCH(64, 64);
+#undef W_LAUNCH
+  const long long nel = (long long)Cout * Cin;
+  int groups = 1;  // about 16 chunks per thread, at most 16 groups
+  while (groups < 16 && nchunks > 16 * groups) groups *= 2;
+  hipLaunchKernelGGL(conv1x1_wrw_reduce_kernel,
+                     dim3((unsigned)(nel / (4 * (256 / groups)))), block, 0,
+                     stream, part, (bf16*)dw, nel, nchunks, groups,
+                     accumulate);
 }
