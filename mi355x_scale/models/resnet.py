@@ -32,21 +32,29 @@ def _conv3x3(cin: int, cout: int, stride: int = 1) -> nn.Conv2d:
 
 
 def _conv1x1(cin: int, cout: int, stride: int = 1) -> nn.Conv2d:
-    if stride == 1:
-        # MFMA pointwise GEMM, opt-in (ops/csrc/conv1x1.hip)
-        return Conv1x1(cin, cout)
-    return nn.Conv2d(cin, cout, 1, stride=stride, bias=False)
+    # MFMA pointwise GEMM, stride 1 and 2, opt-in (ops/csrc/conv1x1.hip)
+    return Conv1x1(cin, cout, stride)
 
 
 def _conv_bn(conv: nn.Conv2d, bn: FusedBNReLU2d, x: torch.Tensor,
              residual: Optional[torch.Tensor] = None) -> torch.Tensor:
     """``bn(conv(x), residual)``. A pointwise conv on its HIP path has
     already summed the BN's batch statistics in its epilogue, so the BN
-    skips its reduce pass over the conv's output."""
+    skips its reduce pass over the conv's output. Serves the main path
+    and, through ``_Downsample``, the skip path."""
     if bn.training and isinstance(conv, Conv1x1) and conv.stats_ok(x):
         out, partial = conv.forward_with_stats(x)
         return bn(out, residual=residual, partial=partial)
     return bn(conv(x), residual=residual)
+
+
+class _Downsample(nn.Sequential):
+    """The skip path's conv + BN pair. A plain ``nn.Sequential`` in keys
+    and module order; its forward goes through ``_conv_bn`` so that the
+    conv's epilogue sums reach the BN."""
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        return _conv_bn(self[0], self[1], x)
 
 
 def _join_twin(x: torch.Tensor) -> torch.Tensor:
@@ -137,7 +145,7 @@ class ResNet(nn.Module):
                     stride: int = 1) -> nn.Sequential:
         downsample = None
         if stride != 1 or self.inplanes != planes * block.expansion:
-            downsample = nn.Sequential(
+            downsample = _Downsample(
                 _conv1x1(self.inplanes, planes * block.expansion, stride),
                 FusedBNReLU2d(planes * block.expansion, relu=False),
             )

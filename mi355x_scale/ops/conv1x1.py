@@ -1,4 +1,4 @@
-"""MFMA pointwise (1x1, stride 1) convolution, NHWC bf16.
+"""MFMA pointwise (1x1, stride 1 and 2) convolution, NHWC bf16.
 
 Two thirds of a Bottleneck network's convs are 1x1 (the reference trains
 torchvision resnet50, ``deep_learning/
@@ -58,6 +58,27 @@ shapes are HBM-bound (operands at 4.9-5.7 TB/s of 8); from H = 28 down
 the bound is the tiles' re-reads through L2 and/or load latency
 (BASELINE.md has the byte counts). Default-OFF as well.
 
+Stride 2 (``Conv1x1(cin, cout, stride=2)``, the downsample projections
+of every ResNet here): the same GEMMs over the ``M' = N*Ho*Wo`` rows of
+the small map (``Ho = (H+1)//2``, ``Wo = (W+1)//2``) with the rows of the
+large map gathered, ``(n, ho, wo) <-> (n, 2ho, 2wo)``; each is still Cin
+contiguous values. The forward gathers its A rows (statistics epilogue
+and partial layout unchanged, so ``forward_with_stats`` serves both
+strides), the weight-grad gathers its X panel rows, and the data-grad
+scatters: it writes the product row to the even pixel and zeros to the
+other pixels of its 2x2 cell, so one launch writes all of ``dx`` and
+there is no memset. The row map is two mul-hi divisions with host-computed
+reciprocals. Same two switches, same gate. Measured at batch 212 on the
+six downsample shapes (benchmarks/bench_conv1x1_s2.py, three alternating
+rounds, table in BASELINE.md): every kernel is faster than MIOpen on the
+three ResNet-18/34 shapes (fwd + stats 12-19 us against 23-28, dgrad 1.9x,
+wrw + add 1.4-1.5x); on ResNet-50's the plain forward LOSES on 256->512@56
+and 512->1024@28, fwd + stats is level on 256->512@56 and faster on the
+other two, dgrad is faster on two and level on 512->1024@28, wrw faster on
+two and level on 256->512@56. Steps with both switches on: ResNet-50
+22.84 -> 22.63 ms (faster by the rule), ResNet-18 7.59 -> 7.53 ms by the
+medians but LEVEL by the rule. Default-OFF like stride 1.
+
 ``Conv1x1`` subclasses ``nn.Conv2d`` (state-dict compatible, same init).
 When enabled, the HIP path takes CUDA bf16 channels-last inputs and a
 bf16 weight with Cin, Cout in {64, 128, ..., 2048}; everything else
@@ -72,12 +93,14 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 
-def _fwd(x: torch.Tensor, weight: torch.Tensor, stats: bool):
+def _fwd(x: torch.Tensor, weight: torch.Tensor, stats: bool, stride: int):
     """Launch the forward GEMM. ``stats``: also fill the BN partial sums of
     the output (fp32 ``[2*Cout][nblocks]``, the layout ``bn_fwd_finalize``
     reads); otherwise ``partial`` is None."""
     from . import _C
     N, _, H, W = x.shape
+    if stride == 2:
+        H, W = (H + 1) // 2, (W + 1) // 2
     cout = weight.shape[0]
     out = torch.empty((N, cout, H, W), dtype=torch.bfloat16, device=x.device,
                       memory_format=torch.channels_last)
@@ -86,60 +109,65 @@ def _fwd(x: torch.Tensor, weight: torch.Tensor, stats: bool):
         partial = torch.empty(2 * cout * _C.conv1x1_fwd_blocks(N * H * W),
                               dtype=torch.float32, device=x.device)
     # the kernel addresses raw NHWC storage: hand the physical views over
-    _C.conv1x1_fwd(x.permute(0, 2, 3, 1), weight, out.permute(0, 2, 3, 1),
-                   partial)
+    fwd = _C.conv1x1_s2_fwd if stride == 2 else _C.conv1x1_fwd
+    fwd(x.permute(0, 2, 3, 1), weight, out.permute(0, 2, 3, 1), partial)
     return out, partial
 
 
 def _bwd(ctx, dy: torch.Tensor):
     from . import _C
     x, weight = ctx.saved_tensors
+    stride = ctx.stride
     if dy.dtype != torch.bfloat16:
         dy = dy.to(torch.bfloat16)
     dy = dy.contiguous(memory_format=torch.channels_last)
     dx = dw = None
     if ctx.needs_input_grad[0]:
+        # the stride-2 kernel writes the skipped pixels' zeros itself
         dx = torch.empty_like(x)
-        _C.conv1x1_dgrad(dy.permute(0, 2, 3, 1), weight,
-                         dx.permute(0, 2, 3, 1))
+        dgrad = _C.conv1x1_s2_dgrad if stride == 2 else _C.conv1x1_dgrad
+        dgrad(dy.permute(0, 2, 3, 1), weight, dx.permute(0, 2, 3, 1))
     if ctx.needs_input_grad[1]:
         if os.environ.get("MI355X_CONV1X1_WRW", "0") == "1":
-            dw = _wrw(x, dy, weight)
+            dw = _wrw(x, dy, weight, stride)
         else:
             dw = torch.ops.aten.convolution_backward(
-                dy, x, weight, None, [1, 1], [0, 0], [1, 1], False, [0, 0],
-                1, [False, True, False])[1]
-    return dx, dw
+                dy, x, weight, None, [stride, stride], [0, 0], [1, 1], False,
+                [0, 0], 1, [False, True, False])[1]
+    return dx, dw, None
 
 
-def _wrw(x: torch.Tensor, dy: torch.Tensor, weight: torch.Tensor):
+def _wrw(x: torch.Tensor, dy: torch.Tensor, weight: torch.Tensor,
+         stride: int):
     """Weight-grad on the HIP kernels. Returns a fresh ``dw``, or None after
     adding it into ``weight.grad`` in place (under graph capture, when the
     grad is a dense bf16 tensor of the weight's shape; the weight is dense
     wherever the HIP path engages, so the two share one layout)."""
     from . import _C
-    N, cin, H, W = x.shape
-    cout = weight.shape[0]
+    cin, cout = x.shape[1], weight.shape[0]
+    rows = dy.shape[0] * dy.shape[2] * dy.shape[3]  # the reduction length
+    wrw = _C.conv1x1_s2_wrw if stride == 2 else _C.conv1x1_wrw
     with torch.cuda.device(x.device):  # the chunk rule asks this device
-        nch = _C.conv1x1_wrw_nchunks(N * H * W, cin, cout)
+        nch = _C.conv1x1_wrw_nchunks(rows, cin, cout)
     part = torch.empty(nch * cout * cin, dtype=torch.float32, device=x.device)
     xn, dyn = x.permute(0, 2, 3, 1), dy.permute(0, 2, 3, 1)
     g = weight.grad
     if (torch.cuda.is_current_stream_capturing() and g is not None
             and g.dtype == torch.bfloat16 and g.device == weight.device
             and g.shape == weight.shape and g.is_contiguous()):
-        _C.conv1x1_wrw(xn, dyn, part, g, True)
+        wrw(xn, dyn, part, g, True)
         return None
     dw = torch.empty_like(weight)
-    _C.conv1x1_wrw(xn, dyn, part, dw)
+    wrw(xn, dyn, part, dw)
     return dw
 
 
 class _Conv1x1Fn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x: torch.Tensor, weight: torch.Tensor):
-        out, _ = _fwd(x, weight, False)
+    def forward(ctx, x: torch.Tensor, weight: torch.Tensor, stride: int):
+        out, _ = _fwd(x, weight, False, stride)
         ctx.save_for_backward(x, weight)
+        ctx.stride = stride
         return out
 
     @staticmethod
@@ -152,9 +180,10 @@ class _Conv1x1StatsFn(torch.autograd.Function):
     (non-differentiable); backward is ``_Conv1x1Fn``'s."""
 
     @staticmethod
-    def forward(ctx, x: torch.Tensor, weight: torch.Tensor):
-        out, partial = _fwd(x, weight, True)
+    def forward(ctx, x: torch.Tensor, weight: torch.Tensor, stride: int):
+        out, partial = _fwd(x, weight, True, stride)
         ctx.save_for_backward(x, weight)
+        ctx.stride = stride
         ctx.mark_non_differentiable(partial)
         # otherwise autograd hands backward a zero-filled tensor of
         # partial's size every step
@@ -164,15 +193,17 @@ class _Conv1x1StatsFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy, _dpartial):
         if dy is None:
-            return None, None
+            return None, None, None
         return _bwd(ctx, dy)
 
 
 class Conv1x1(nn.Conv2d):
-    """1x1/s1 conv (no bias) with the MFMA HIP fast path."""
+    """1x1 conv, stride 1 or 2 (no bias), with the MFMA HIP fast path."""
 
-    def __init__(self, cin: int, cout: int):
-        super().__init__(cin, cout, 1, stride=1, bias=False)
+    def __init__(self, cin: int, cout: int, stride: int = 1):
+        if stride not in (1, 2):
+            raise ValueError(f"Conv1x1: stride must be 1 or 2, got {stride!r}")
+        super().__init__(cin, cout, 1, stride=stride, bias=False)
 
     def _hip_ok(self, x: torch.Tensor) -> bool:
         if os.environ.get("MI355X_CONV1X1", "0") != "1" or not x.is_cuda:
@@ -199,10 +230,10 @@ class Conv1x1(nn.Conv2d):
         of the output for ``FusedBNReLU2d.forward(..., partial=...)``, or
         is None when the HIP path does not engage."""
         if self.stats_ok(x):
-            return _Conv1x1StatsFn.apply(x, self.weight)
+            return _Conv1x1StatsFn.apply(x, self.weight, self.stride[0])
         return self.forward(x), None
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         if self._hip_ok(x):
-            return _Conv1x1Fn.apply(x, self.weight)
-        return F.conv2d(x, self.weight, None, 1, 0)
+            return _Conv1x1Fn.apply(x, self.weight, self.stride[0])
+        return F.conv2d(x, self.weight, None, self.stride[0], 0)

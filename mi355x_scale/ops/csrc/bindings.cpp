@@ -1154,8 +1154,10 @@ int64_t conv1x1_fwd_blocks(int64_t M) { return conv1x1_m_blocks(M); }
 // the [Cout, Cin(,1,1)] weight, all bf16 on the GPU and dense.
 struct _C1Geom { long long M; int Cin, Cout; };
 
-static _C1Geom _check_conv1x1(const torch::Tensor& xi, const torch::Tensor& w,
-                              const torch::Tensor& xo) {
+// dtype, density, device, channel counts and the weight's shape
+static void _check_conv1x1_tensors(const torch::Tensor& xi,
+                                   const torch::Tensor& w,
+                                   const torch::Tensor& xo) {
   for (const torch::Tensor* t : {&xi, &w, &xo})
     TORCH_CHECK(t->is_cuda() && t->scalar_type() == torch::kBFloat16 &&
                     t->is_contiguous() && t->device() == xi.device(),
@@ -1168,6 +1170,12 @@ static _C1Geom _check_conv1x1(const torch::Tensor& xi, const torch::Tensor& w,
               "conv1x1: Cin and Cout must be multiples of 64 up to 2048");
   TORCH_CHECK(w.size(0) == Cout && w.numel() == Cout * Cin,
               "conv1x1: weight must be [Cout, Cin] (1x1, groups 1)");
+}
+
+static _C1Geom _check_conv1x1(const torch::Tensor& xi, const torch::Tensor& w,
+                              const torch::Tensor& xo) {
+  _check_conv1x1_tensors(xi, w, xo);
+  const int64_t Cin = xi.size(-1), Cout = xo.size(-1);
   const int64_t M = xi.numel() / Cin;
   TORCH_CHECK(M > 0 && xo.numel() == M * Cout &&
                   xi.sizes().slice(0, xi.dim() - 1) ==
@@ -1262,7 +1270,113 @@ void conv1x1_wrw(torch::Tensor x, torch::Tensor dy, torch::Tensor part,
                      (int)phase_mask);
 }
 
+// Stride-2 pointwise conv (conv1x1.hip, S2 instantiations): the input-side
+// map is [N,H,W,Cin], the output-side map [N,(H+1)/2,(W+1)/2,Cout]; output
+// pixel (n,ho,wo) pairs with input pixel (n,2ho,2wo).
+extern "C" void launch_conv1x1_s2_fwd(const void* x, const void* w, void* out,
+                                      float* partial, int N, int H, int W,
+                                      int Cin, int Cout, hipStream_t stream,
+                                      int phase_mask);
+extern "C" void launch_conv1x1_s2_dgrad(const void* dy, const void* w,
+                                        void* dx, int N, int H, int W,
+                                        int Cin, int Cout, hipStream_t stream,
+                                        int phase_mask);
+extern "C" void launch_conv1x1_s2_wrw(const void* x, const void* dy,
+                                      float* part, void* dw, int N, int H,
+                                      int W, int Cin, int Cout, int nchunks,
+                                      int accumulate, hipStream_t stream,
+                                      int phase_mask);
+
+// M counts the rows of the SMALL map (the GEMMs' row count)
+struct _C1S2Geom { long long M; int N, H, W, Cin, Cout; };
+
+static _C1S2Geom _check_conv1x1_s2(const torch::Tensor& xi,
+                                   const torch::Tensor& w,
+                                   const torch::Tensor& xo) {
+  _check_conv1x1_tensors(xi, w, xo);
+  TORCH_CHECK(xi.dim() == 4, "conv1x1_s2: maps must be [N, H, W, C]");
+  const int64_t N = xi.size(0), H = xi.size(1), W = xi.size(2);
+  const int64_t Cin = xi.size(3), Cout = xo.size(3);
+  TORCH_CHECK(N > 0 && H > 0 && W > 0 && xo.size(0) == N &&
+                  xo.size(1) == (H + 1) / 2 && xo.size(2) == (W + 1) / 2,
+              "conv1x1_s2: the small map must be [N, (H+1)/2, (W+1)/2, C]");
+  const int64_t Mi = N * H * W, M = xo.numel() / Cout;
+  TORCH_CHECK(Mi < (1LL << 31) - 128 && M < (1LL << 31) - 128 &&
+                  conv1x1_fwd_blocks(M) * (std::max(Cin, Cout) / 64) <
+                      (1LL << 31),
+              "conv1x1_s2: too many rows for one launch");
+  return {(long long)M, (int)N, (int)H, (int)W, (int)Cin, (int)Cout};
+}
+
+// out [N,Ho,Wo,Cout] = x[:, ::2, ::2] . w[Cout,Cin]^T; ``partial`` as in
+// conv1x1_fwd with M' = N*Ho*Wo rows.
+void conv1x1_s2_fwd(torch::Tensor x, torch::Tensor w, torch::Tensor out,
+                    c10::optional<torch::Tensor> partial = c10::nullopt,
+                    int64_t phase_mask = 7) {
+  const _C1S2Geom g = _check_conv1x1_s2(x, w, out);
+  float* partial_p = nullptr;
+  if (partial.has_value()) {
+    const torch::Tensor& p = *partial;
+    TORCH_CHECK(p.is_cuda() && p.scalar_type() == torch::kFloat32 &&
+                    p.is_contiguous() && p.device() == x.device() &&
+                    p.numel() == 2 * g.Cout * conv1x1_fwd_blocks(g.M),
+                "partial must be fp32 [2*Cout*conv1x1_fwd_blocks(M')]");
+    partial_p = p.data_ptr<float>();
+  }
+  launch_conv1x1_s2_fwd(x.data_ptr(), w.data_ptr(), out.data_ptr(), partial_p,
+                        g.N, g.H, g.W, g.Cin, g.Cout,
+                        at::cuda::getCurrentHIPStream().stream(),
+                        (int)phase_mask);
+}
+
+// dx [N,H,W,Cin]: dy . w at the even pixels, zero at every other one. The
+// one launch writes every element of dx (torch.empty serves).
+void conv1x1_s2_dgrad(torch::Tensor dy, torch::Tensor w, torch::Tensor dx,
+                      int64_t phase_mask = 7) {
+  const _C1S2Geom g = _check_conv1x1_s2(dx, w, dy);
+  launch_conv1x1_s2_dgrad(dy.data_ptr(), w.data_ptr(), dx.data_ptr(), g.N,
+                          g.H, g.W, g.Cin, g.Cout,
+                          at::cuda::getCurrentHIPStream().stream(),
+                          (int)phase_mask);
+}
+
+// dw = dy^T . x[:, ::2, ::2]; ``part``, ``accumulate`` and ``chunks`` as in
+// conv1x1_wrw with M' = N*Ho*Wo rows.
+void conv1x1_s2_wrw(torch::Tensor x, torch::Tensor dy, torch::Tensor part,
+                    torch::Tensor dw, bool accumulate = false,
+                    int64_t chunks = 0, int64_t phase_mask = 7) {
+  const _C1S2Geom g = _check_conv1x1_s2(x, dw, dy);
+  const c10::DeviceGuard guard(x.device());
+  const int64_t nch = conv1x1_wrw_nchunks(g.M, g.Cin, g.Cout, chunks);
+  TORCH_CHECK(part.is_cuda() && part.scalar_type() == torch::kFloat32 &&
+                  part.is_contiguous() && part.device() == x.device() &&
+                  part.numel() == nch * g.Cout * g.Cin,
+              "part must be fp32 [conv1x1_wrw_nchunks*Cout*Cin] (", nch,
+              " chunks)");
+  TORCH_CHECK(nch * (g.Cin / 64) * (g.Cout / 64) < (1LL << 31),
+              "conv1x1_wrw: too many blocks for one launch");
+  launch_conv1x1_s2_wrw(x.data_ptr(), dy.data_ptr(), part.data_ptr<float>(),
+                        dw.data_ptr(), g.N, g.H, g.W, g.Cin, g.Cout, (int)nch,
+                        accumulate ? 1 : 0,
+                        at::cuda::getCurrentHIPStream().stream(),
+                        (int)phase_mask);
+}
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
+  m.def("conv1x1_s2_fwd", &conv1x1_s2_fwd,
+        "MFMA pointwise stride-2 conv fwd (NHWC bf16), optional BN partials",
+        pybind11::arg("x"), pybind11::arg("w"), pybind11::arg("out"),
+        pybind11::arg("partial") = pybind11::none(),
+        pybind11::arg("phase_mask") = 7);
+  m.def("conv1x1_s2_dgrad", &conv1x1_s2_dgrad,
+        "MFMA pointwise stride-2 conv data-grad: writes all of dx",
+        pybind11::arg("dy"), pybind11::arg("w"), pybind11::arg("dx"),
+        pybind11::arg("phase_mask") = 7);
+  m.def("conv1x1_s2_wrw", &conv1x1_s2_wrw,
+        "MFMA pointwise stride-2 conv weight-grad (as conv1x1_wrw)",
+        pybind11::arg("x"), pybind11::arg("dy"), pybind11::arg("part"),
+        pybind11::arg("dw"), pybind11::arg("accumulate") = false,
+        pybind11::arg("chunks") = 0, pybind11::arg("phase_mask") = 7);
   m.def("conv1x1_wrw", &conv1x1_wrw,
         "MFMA pointwise conv weight-grad (split over M, fp32 partials, "
         "bf16 store or accumulate into dw)",

@@ -1,6 +1,8 @@
-// Hand-written MFMA pointwise (1x1, stride 1) convolution for gfx950,
+// Hand-written MFMA pointwise (1x1, stride 1 and 2) convolution for gfx950,
 // NHWC bf16: forward, forward with BatchNorm statistics in the epilogue,
-// data-grad, and (second half of this file) a split-K weight-grad.
+// data-grad, and (second half of this file) a split-K weight-grad. The
+// stride-2 variants (the downsample projections; end of this comment) are
+// the S2 = true instantiations of the same two kernel templates.
 //
 // Why: two thirds of a Bottleneck network's convs are 1x1 (the reference
 // trains torchvision resnet50, deep_learning/
@@ -50,8 +52,36 @@
 //     lanes sharing a column add by shuffle, the four waves through LDS
 //     in a fixed order; one thread per column writes the two slots. No
 //     atomics: bit-reproducible. Zero rows add nothing to the sums.
+//
+// Stride 2 (X [N,H,W,Cin]; Y, dY [N,Ho,Wo,Cout], Ho = (H+1)/2, Wo =
+// (W+1)/2, M' = N*Ho*Wo): the same GEMMs over M' rows with the rows of
+// the large map gathered. Output pixel m' = (n, ho, wo) pairs with input
+// pixel (n, 2ho, 2wo), still Cin contiguous values, so every load and
+// store stays 16 bytes along the channel axis and the LDS tiles, the
+// statistics epilogue and the partial layouts are the stride-1 ones.
+//   * row map: m' -> (n*H + 2ho)*W + 2wo by two 32-bit divisions (by
+//     Ho*Wo, then by Wo), each ONE v_mul_hi_u32 with a host-computed
+//     floor(2^32 / d) passed in the kernel arguments plus one conditional
+//     correction (the product underestimates the quotient by at most one
+//     for every 32-bit dividend). No 64-bit division, no loop over image
+//     rows: the cost is the same for every Wo.
+//   * forward: the four A rows a thread stages keep four gathered base
+//     pointers computed once before the K loop (8 VGPRs).
+//   * data-grad: the A operand (dY) is contiguous; the epilogue scatters.
+//     The 2x2 input cells (2ho..2ho+1, 2wo..2wo+1), clipped to H and W,
+//     tile the large map exactly, so the lanes that hold 16 bytes of
+//     product row m' store them to the cell's top-left pixel and 16-byte
+//     zero vectors to the cell's other in-bounds pixels: every element of
+//     dX is written exactly once by this one launch (no memset, no
+//     atomics, dX may be uninitialised).
+//   * weight-grad: the dY panel is contiguous, the X panel row of each
+//     32-row K-step comes through the row map, once per thread per step.
+// S2 is a template parameter and the stride-1 geometry argument an empty
+// struct: the stride-1 instantiations compile to the code they had.
 #include <hip/hip_runtime.h>
 #include <hip/hip_bf16.h>
+
+#include <type_traits>
 
 #define BM 128                  // output rows per block
 #define BN 64                   // output columns per block
@@ -80,15 +110,57 @@ __device__ __forceinline__ bf16x8 tr_frag(const bf16* p0, const bf16* p1) {
   return __builtin_bit_cast(bf16x8, v);
 }
 
+// Stride-2 geometry: the large map's H and W, the small map's Wo and
+// Ho*Wo, and floor(2^32 / d) for those two divisors (2^32 - 1 for d = 1).
+struct C1S2 {
+  int H, W, Wo, HoWo;
+  unsigned rWo, rHoWo;
+};
+struct C1S1 {};  // stride 1 has no geometry
+template <bool S2>
+using C1Geo = typename std::conditional<S2, C1S2, C1S1>::type;
+
+// q = m / d, m -= q * d, for any 32-bit m: m * floor(2^32/d) / 2^32 lies
+// in (m/d - 1, m/d], so its floor is the quotient or one below it
+__device__ __forceinline__ unsigned s2_divmod(unsigned& m, unsigned d,
+                                              unsigned rd) {
+  unsigned q = __umulhi(m, rd);
+  m -= q * d;
+  if (m >= d) {
+    m -= d;
+    ++q;
+  }
+  return q;
+}
+
+// small-map row m' = (n*Ho + ho)*Wo + wo -> (n, 2ho, 2wo) of the large map
+__device__ __forceinline__ void s2_pixel(unsigned m, const C1S2& g,
+                                         unsigned& n, unsigned& hi,
+                                         unsigned& wi) {
+  n = s2_divmod(m, (unsigned)g.HoWo, g.rHoWo);
+  hi = 2 * s2_divmod(m, (unsigned)g.Wo, g.rWo);
+  wi = 2 * m;
+}
+
+// ... -> its row in the large map (below 2^31: the bindings check)
+__device__ __forceinline__ unsigned s2_row(unsigned m, const C1S2& g) {
+  unsigned n, hi, wi;
+  s2_pixel(m, g, n, hi, wi);
+  return (n * g.H + hi) * g.W + wi;
+}
+
 // Out[M][N] = A[M][K] . B, with B = W[N][K] (C1_FWD*) or W[K][N]
 // (C1_DGRAD). grid = ceil(M / BM) * (N / BN), column tiles fastest.
 // phase_mask: 1 = global loads + LDS staging, 4 = MFMA, 2 = epilogue.
-template <int MODE>
+// S2: M counts the small map's rows; the forward gathers its A rows from
+// the large map and the data-grad scatters its output rows into it.
+template <int MODE, bool S2 = false>
 __global__ __launch_bounds__(256, 3) void conv1x1_gemm_kernel(
     const bf16* __restrict__ A, const bf16* __restrict__ B,
     bf16* __restrict__ Out,
     float* __restrict__ partial,  // [2*N][ceil(M / BM)], C1_FWD_STATS only
-    int M, int N, int K, int ntn, int phase_mask) {
+    int M, int N, int K, int ntn, int phase_mask, const C1Geo<S2> g) {
+  constexpr bool GATHER = S2 && MODE != C1_DGRAD;
   __shared__ __attribute__((aligned(16))) bf16 smem[2 * (BM + BN) * BK];
   bf16* const As = smem;                // [2][BM * BK]
   bf16* const Bs = smem + 2 * BM * BK;  // [2][BN * BK]
@@ -118,6 +190,15 @@ __global__ __launch_bounds__(256, 3) void conv1x1_gemm_kernel(
   bool alive[4];
 #pragma unroll
   for (int u = 0; u < 4; ++u) alive[u] = m0 + srow + 32 * u < M;
+  // stride-2 forward: the four A rows lie at gathered rows of the large map
+  const bf16* pag[4];
+  if constexpr (GATHER) {
+#pragma unroll
+    for (int u = 0; u < 4; ++u)
+      pag[u] = alive[u]
+          ? A + (long long)s2_row(m0 + srow + 32 * u, g) * K + sch * 8
+          : A;
+  }
 
   // operand addressing (element offsets inside one tile)
   const int sw = l16 & 7;               // row & 7 of every row this lane reads
@@ -144,10 +225,16 @@ __global__ __launch_bounds__(256, 3) void conv1x1_gemm_kernel(
 
 #define C1_GLOAD(ks)                                                        \
   {                                                                         \
-    _Pragma("unroll") for (int u = 0; u < 4; ++u)                           \
-      ra[u] = alive[u] ? *reinterpret_cast<const bf16x8*>(                  \
-                             pa + (long long)u * 32 * K + (ks) * BK)        \
-                       : zv;                                                \
+    _Pragma("unroll") for (int u = 0; u < 4; ++u) {                         \
+      if constexpr (GATHER)                                                 \
+        ra[u] = alive[u] ? *reinterpret_cast<const bf16x8*>(                \
+                               pag[u] + (ks) * BK)                          \
+                         : zv;                                              \
+      else                                                                  \
+        ra[u] = alive[u] ? *reinterpret_cast<const bf16x8*>(                \
+                               pa + (long long)u * 32 * K + (ks) * BK)      \
+                         : zv;                                              \
+    }                                                                       \
     _Pragma("unroll") for (int u = 0; u < 2; ++u)                           \
       rb[u] = *reinterpret_cast<const bf16x8*>(                             \
           pb + (long long)u * bstep + (long long)(ks) * bkstep);            \
@@ -238,8 +325,25 @@ __global__ __launch_bounds__(256, 3) void conv1x1_gemm_kernel(
     const int rl = v >> 3, j8 = (v & 7) * 8;
     const int row = m0 + wave * 32 + rl;
     const bf16x8 val = *reinterpret_cast<const bf16x8*>(tw + rl * OTROW + j8);
-    if (row < M)
-      *reinterpret_cast<bf16x8*>(Out + (long long)row * N + n0 + j8) = val;
+    if constexpr (S2 && MODE == C1_DGRAD) {
+      // the row goes to the top-left pixel of its 2x2 cell of the large
+      // map, zeros to the cell's other pixels inside H x W
+      if (row < M) {
+        unsigned n, hi, wi;
+        s2_pixel(row, g, n, hi, wi);
+        bf16* const o =
+            Out + (long long)((n * g.H + hi) * g.W + wi) * N + n0 + j8;
+        const bool right = (int)wi + 1 < g.W, below = (int)hi + 1 < g.H;
+        const long long down = (long long)g.W * N;
+        *reinterpret_cast<bf16x8*>(o) = val;
+        if (right) *reinterpret_cast<bf16x8*>(o + N) = zv;
+        if (below) *reinterpret_cast<bf16x8*>(o + down) = zv;
+        if (right && below) *reinterpret_cast<bf16x8*>(o + down + N) = zv;
+      }
+    } else {
+      if (row < M)
+        *reinterpret_cast<bf16x8*>(Out + (long long)row * N + n0 + j8) = val;
+    }
   }
 
   if (MODE == C1_FWD_STATS) {
@@ -287,11 +391,12 @@ extern "C" void launch_conv1x1_fwd(const void* x, const void* w, void* out,
   if (partial)
     hipLaunchKernelGGL(conv1x1_gemm_kernel<C1_FWD_STATS>, grid, block, 0,
                        stream, (const bf16*)x, (const bf16*)w, (bf16*)out,
-                       partial, (int)M, Cout, Cin, ntn, phase_mask);
+                       partial, (int)M, Cout, Cin, ntn, phase_mask, C1S1{});
   else
     hipLaunchKernelGGL(conv1x1_gemm_kernel<C1_FWD>, grid, block, 0, stream,
                        (const bf16*)x, (const bf16*)w, (bf16*)out,
-                       (float*)nullptr, (int)M, Cout, Cin, ntn, phase_mask);
+                       (float*)nullptr, (int)M, Cout, Cin, ntn, phase_mask,
+                       C1S1{});
 }
 
 extern "C" void launch_conv1x1_dgrad(const void* dy, const void* w, void* dx,
@@ -301,7 +406,59 @@ extern "C" void launch_conv1x1_dgrad(const void* dy, const void* w, void* dx,
   const dim3 grid(conv1x1_m_blocks(M) * ntn), block(256);
   hipLaunchKernelGGL(conv1x1_gemm_kernel<C1_DGRAD>, grid, block, 0, stream,
                      (const bf16*)dy, (const bf16*)w, (bf16*)dx,
-                     (float*)nullptr, (int)M, Cin, Cout, ntn, phase_mask);
+                     (float*)nullptr, (int)M, Cin, Cout, ntn, phase_mask,
+                     C1S1{});
+}
+
+// floor(2^32 / d), saturated for d = 1: the multiplier s2_divmod takes
+static unsigned s2_recip(long long d) {
+  const long long r = (1LL << 32) / d;
+  return r > 0xffffffffLL ? 0xffffffffu : (unsigned)r;
+}
+
+static C1S2 s2_geom(int H, int W) {
+  const int Ho = (H + 1) / 2, Wo = (W + 1) / 2;
+  return {H, W, Wo, Ho * Wo, s2_recip(Wo), s2_recip((long long)Ho * Wo)};
+}
+
+// rows of the small map: N * ((H+1)/2) * ((W+1)/2)
+static long long conv1x1_s2_rows(long long N, long long H, long long W) {
+  return N * ((H + 1) / 2) * ((W + 1) / 2);
+}
+
+// Stride 2: x [N,H,W,Cin] -> out [N,Ho,Wo,Cout]; ``partial`` as above with
+// M' = conv1x1_s2_rows(N, H, W) in the place of M.
+extern "C" void launch_conv1x1_s2_fwd(const void* x, const void* w, void* out,
+                                      float* partial, int N, int H, int W,
+                                      int Cin, int Cout, hipStream_t stream,
+                                      int phase_mask) {
+  const long long M = conv1x1_s2_rows(N, H, W);
+  const int ntn = Cout / BN;
+  const dim3 grid(conv1x1_m_blocks(M) * ntn), block(256);
+  if (partial)
+    hipLaunchKernelGGL((conv1x1_gemm_kernel<C1_FWD_STATS, true>), grid, block,
+                       0, stream, (const bf16*)x, (const bf16*)w, (bf16*)out,
+                       partial, (int)M, Cout, Cin, ntn, phase_mask,
+                       s2_geom(H, W));
+  else
+    hipLaunchKernelGGL((conv1x1_gemm_kernel<C1_FWD, true>), grid, block, 0,
+                       stream, (const bf16*)x, (const bf16*)w, (bf16*)out,
+                       (float*)nullptr, (int)M, Cout, Cin, ntn, phase_mask,
+                       s2_geom(H, W));
+}
+
+// Stride 2: dx [N,H,W,Cin] from dy [N,Ho,Wo,Cout]; writes all of dx.
+extern "C" void launch_conv1x1_s2_dgrad(const void* dy, const void* w,
+                                        void* dx, int N, int H, int W,
+                                        int Cin, int Cout, hipStream_t stream,
+                                        int phase_mask) {
+  const long long M = conv1x1_s2_rows(N, H, W);
+  const int ntn = Cin / BN;
+  const dim3 grid(conv1x1_m_blocks(M) * ntn), block(256);
+  hipLaunchKernelGGL((conv1x1_gemm_kernel<C1_DGRAD, true>), grid, block, 0,
+                     stream, (const bf16*)dy, (const bf16*)w, (bf16*)dx,
+                     (float*)nullptr, (int)M, Cin, Cout, ntn, phase_mask,
+                     s2_geom(H, W));
 }
 
 // ---------------------------------------------------------------------
@@ -375,11 +532,13 @@ __device__ __forceinline__ int wswz(int row, int ch) {
 // part[chunk][Cout][Cin] = sum over the chunk's rows. grid = chunks *
 // tiles; spc = K-steps per chunk (the last chunk may be shorter, never
 // empty). phase_mask: 1 = global loads + LDS staging, 4 = MFMA, 2 = epilogue.
-template <int TCO, int TCI>
+// S2: M counts the rows of dY (the small map) and row m of the X panel is
+// row s2_row(m) of the large map.
+template <int TCO, int TCI, bool S2 = false>
 __global__ __launch_bounds__(256, 4) void conv1x1_wrw_kernel(
     const bf16* __restrict__ X, const bf16* __restrict__ dY,
     float* __restrict__ part, int M, int Cin, int Cout, int ntci, int tiles,
-    int spc, int phase_mask) {
+    int spc, int phase_mask, const C1Geo<S2> g) {
   constexpr int PI = TCI / 64, PO = TCO / 64;  // panels per operand
   constexpr int IT = TCI / 32, OT = TCO / 32;  // accumulator tiles per wave
   constexpr int TILE = (PI + PO) * WPANEL;     // one buffer: X panels, dY panels
@@ -401,7 +560,8 @@ __global__ __launch_bounds__(256, 4) void conv1x1_wrw_kernel(
   const int srow = tid >> 3, sch = tid & 7;
   const int sto = wswz(srow, sch);
   const int mrow = s0 * WK + srow;
-  const bf16* px = X + (long long)mrow * Cin + ci0 + sch * 8;
+  const bf16* px = S2 ? X + ci0 + sch * 8  // the row is added per K-step
+                      : X + (long long)mrow * Cin + ci0 + sch * 8;
   const bf16* py = dY + (long long)mrow * Cout + co0 + sch * 8;
   const bf16x8 zv = {(bf16)0.0f, (bf16)0.0f, (bf16)0.0f, (bf16)0.0f,
                      (bf16)0.0f, (bf16)0.0f, (bf16)0.0f, (bf16)0.0f};
@@ -428,10 +588,13 @@ __global__ __launch_bounds__(256, 4) void conv1x1_wrw_kernel(
 #define W_GLOAD(ks)                                                         \
   {                                                                         \
     const bool alive = mrow + (ks) * WK < M;                                \
+    const bf16* pxk;                                                        \
+    if constexpr (S2)                                                       \
+      pxk = px + (long long)s2_row(mrow + (ks) * WK, g) * Cin;              \
+    else                                                                    \
+      pxk = px + (long long)(ks) * WK * Cin;                                \
     _Pragma("unroll") for (int u = 0; u < PI; ++u)                          \
-      rx[u] = alive ? *reinterpret_cast<const bf16x8*>(                     \
-                          px + (long long)(ks) * WK * Cin + u * 64)         \
-                    : zv;                                                   \
+      rx[u] = alive ? *reinterpret_cast<const bf16x8*>(pxk + u * 64) : zv;  \
     _Pragma("unroll") for (int u = 0; u < PO; ++u)                          \
       ry[u] = alive ? *reinterpret_cast<const bf16x8*>(                     \
                           py + (long long)(ks) * WK * Cout + u * 64)        \
@@ -580,19 +743,20 @@ extern "C" int conv1x1_wrw_chunks(long long M, int Cin, int Cout, int req) {
 
 // ``nchunks`` is a value conv1x1_wrw_chunks returned; part holds
 // nchunks * Cout * Cin floats, every one of which is written.
-extern "C" void launch_conv1x1_wrw(const void* x, const void* dy, float* part,
-                                   void* dw, long long M, int Cin, int Cout,
-                                   int nchunks, int accumulate,
-                                   hipStream_t stream, int phase_mask) {
+template <bool S2>
+static void wrw_launch(const void* x, const void* dy, float* part, void* dw,
+                       long long M, int Cin, int Cout, int nchunks,
+                       int accumulate, hipStream_t stream, int phase_mask,
+                       const C1Geo<S2> g) {
   const int tci = wrw_side(Cin), tco = wrw_side(Cout);
   const int ntci = Cin / tci, tiles = wrw_tiles(Cin, Cout);
   const long long steps = (M + WK - 1) / WK;
   const int spc = (int)((steps + nchunks - 1) / nchunks);
   const dim3 grid(nchunks * tiles), block(256);
 #define W_LAUNCH(TCO, TCI)                                                  \
-  hipLaunchKernelGGL((conv1x1_wrw_kernel<TCO, TCI>), grid, block, 0,        \
+  hipLaunchKernelGGL((conv1x1_wrw_kernel<TCO, TCI, S2>), grid, block, 0,    \
                      stream, (const bf16*)x, (const bf16*)dy, part, (int)M, \
-                     Cin, Cout, ntci, tiles, spc, phase_mask)
+                     Cin, Cout, ntci, tiles, spc, phase_mask, g)
   if (tco == 128 && tci == 128) W_LAUNCH(128, 128);
   else if (tco == 128) W_LAUNCH(128, 64);
   else if (tci == 128) W_LAUNCH(64, 128);
@@ -605,4 +769,23 @@ extern "C" void launch_conv1x1_wrw(const void* x, const void* dy, float* part,
                      dim3((unsigned)(nel / (4 * (256 / groups)))), block, 0,
                      stream, part, (bf16*)dw, nel, nchunks, groups,
                      accumulate);
+}
+
+extern "C" void launch_conv1x1_wrw(const void* x, const void* dy, float* part,
+                                   void* dw, long long M, int Cin, int Cout,
+                                   int nchunks, int accumulate,
+                                   hipStream_t stream, int phase_mask) {
+  wrw_launch<false>(x, dy, part, dw, M, Cin, Cout, nchunks, accumulate,
+                    stream, phase_mask, C1S1{});
+}
+
+// Stride 2: x [N,H,W,Cin], dy [N,Ho,Wo,Cout]; ``nchunks`` is what
+// conv1x1_wrw_chunks returned for M' = conv1x1_s2_rows(N, H, W).
+extern "C" void launch_conv1x1_s2_wrw(const void* x, const void* dy,
+                                      float* part, void* dw, int N, int H,
+                                      int W, int Cin, int Cout, int nchunks,
+                                      int accumulate, hipStream_t stream,
+                                      int phase_mask) {
+  wrw_launch<true>(x, dy, part, dw, conv1x1_s2_rows(N, H, W), Cin, Cout,
+                   nchunks, accumulate, stream, phase_mask, s2_geom(H, W));
 }
