@@ -26,7 +26,8 @@ from ..ops.stemconv import StemConv2d
 
 def _conv3x3(cin: int, cout: int, stride: int = 1) -> nn.Conv2d:
     if stride == 1 and cin == cout:
-        # MFMA weight-grad fast path (ops/csrc/conv3x3wrw.hip)
+        # opt-in MFMA paths: forward + BN statistics and data-grad
+        # (ops/csrc/conv3x3.hip), weight-grad (ops/csrc/conv3x3wrw.hip)
         return Conv3x3(cin, cout)
     return nn.Conv2d(cin, cout, 3, stride=stride, padding=1, bias=False)
 
@@ -38,11 +39,12 @@ def _conv1x1(cin: int, cout: int, stride: int = 1) -> nn.Conv2d:
 
 def _conv_bn(conv: nn.Conv2d, bn: FusedBNReLU2d, x: torch.Tensor,
              residual: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """``bn(conv(x), residual)``. A pointwise conv on its HIP path has
-    already summed the BN's batch statistics in its epilogue, so the BN
-    skips its reduce pass over the conv's output. Serves the main path
-    and, through ``_Downsample``, the skip path."""
-    if bn.training and isinstance(conv, Conv1x1) and conv.stats_ok(x):
+    """``bn(conv(x), residual)``. A pointwise or a stride-1 3x3 conv on its
+    HIP path has already summed the BN's batch statistics in its epilogue,
+    so the BN skips its reduce pass over the conv's output. Serves the
+    main path and, through ``_Downsample``, the skip path."""
+    if (bn.training and isinstance(conv, (Conv1x1, Conv3x3))
+            and conv.stats_ok(x)):
         out, partial = conv.forward_with_stats(x)
         return bn(out, residual=residual, partial=partial)
     return bn(conv(x), residual=residual)
@@ -85,8 +87,8 @@ class BasicBlock(nn.Module):
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         skip = _join_twin(x)
         identity = skip if self.downsample is None else self.downsample(skip)
-        out = self.bn1(self.conv1(x))
-        return self.bn2(self.conv2(out), residual=identity)
+        out = _conv_bn(self.conv1, self.bn1, x)
+        return _conv_bn(self.conv2, self.bn2, out, residual=identity)
 
 
 class Bottleneck(nn.Module):
@@ -107,7 +109,7 @@ class Bottleneck(nn.Module):
         skip = _join_twin(x)
         identity = skip if self.downsample is None else self.downsample(skip)
         out = _conv_bn(self.conv1, self.bn1, x)
-        out = self.bn2(self.conv2(out))
+        out = _conv_bn(self.conv2, self.bn2, out)
         return _conv_bn(self.conv3, self.bn3, out, residual=identity)
 
 

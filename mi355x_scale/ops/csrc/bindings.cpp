@@ -1362,7 +1362,108 @@ void conv1x1_s2_wrw(torch::Tensor x, torch::Tensor dy, torch::Tensor part,
                         (int)phase_mask);
 }
 
+// 3x3 / stride 1 / pad 1 conv over raw NHWC storage (conv3x3.hip): forward
+// (optionally with BN partial sums) and, on a repacked weight, data-grad.
+extern "C" int conv3x3_m_blocks(long long N, long long H, long long W);
+extern "C" void launch_conv3x3_fwd(const void* x, const void* w, void* out,
+                                   float* partial, int N, int H, int W,
+                                   int Cin, int Cout, hipStream_t stream,
+                                   int phase_mask);
+extern "C" void launch_conv3x3_wflip(const void* w, void* wf, int Cin,
+                                     int Cout, hipStream_t stream);
+
+struct _C3Geom { int N, H, W, Cin, Cout; };
+
+// xi [N,H,W,Cin], w [Cout,3,3,Cin] (a channels-last [Cout,Cin,3,3] weight's
+// physical view), xo [N,H,W,Cout]: dense bf16 on one GPU, inside the gate
+static _C3Geom _check_conv3x3(const torch::Tensor& xi, const torch::Tensor& w,
+                              const torch::Tensor& xo) {
+  for (const torch::Tensor* t : {&xi, &w, &xo})
+    TORCH_CHECK(t->is_cuda() && t->scalar_type() == torch::kBFloat16 &&
+                    t->is_contiguous() && t->device() == xi.device() &&
+                    t->dim() == 4,
+                "conv3x3: dense 4-d bf16 GPU tensors on one device");
+  const int64_t N = xi.size(0), H = xi.size(1), W = xi.size(2);
+  const int64_t Cin = xi.size(3), Cout = xo.size(3);
+  TORCH_CHECK(Cin % 64 == 0 && Cin >= 64 && Cin <= 2048 &&
+                  Cout % 64 == 0 && Cout >= 64 && Cout <= 2048,
+              "conv3x3: Cin and Cout must be multiples of 64 up to 2048");
+  TORCH_CHECK(w.size(0) == Cout && w.size(1) == 3 && w.size(2) == 3 &&
+                  w.size(3) == Cin,
+              "conv3x3: weight must be [Cout, 3, 3, Cin]");
+  TORCH_CHECK(xo.size(0) == N && xo.size(1) == H && xo.size(2) == W,
+              "conv3x3: maps must share N, H and W (stride 1, pad 1)");
+  TORCH_CHECK(N >= 1 && H >= 1 && W >= 1 && W <= 64,
+              "conv3x3: needs 1 <= W <= 64, H >= 1, N >= 1");
+  TORCH_CHECK(N < (1LL << 31) && H < (1LL << 24) &&
+                  N * (H + 2) * (W + 2) + 2 * W + 6 < (1LL << 31),
+              "conv3x3: too many pixels for one launch");
+  return {(int)N, (int)H, (int)W, (int)Cin, (int)Cout};
+}
+
+int64_t conv3x3_fwd_blocks(int64_t N, int64_t H, int64_t W) {
+  return conv3x3_m_blocks(N, H, W);
+}
+
+// out = conv(x, w), stride 1, pad 1. With ``partial`` (fp32, 2*Cout*
+// conv3x3_fwd_blocks(N, H, W) elements) the kernel also leaves the BN
+// channel sums of the values it stores, [2C][nblocks] as bn_fwd_finalize
+// reads them.
+void conv3x3_fwd(torch::Tensor x, torch::Tensor w, torch::Tensor out,
+                 c10::optional<torch::Tensor> partial = c10::nullopt,
+                 int64_t phase_mask = 7) {
+  const _C3Geom g = _check_conv3x3(x, w, out);
+  float* partial_p = nullptr;
+  if (partial.has_value()) {
+    const torch::Tensor& p = *partial;
+    TORCH_CHECK(p.is_cuda() && p.scalar_type() == torch::kFloat32 &&
+                    p.is_contiguous() && p.device() == x.device() &&
+                    p.numel() ==
+                        2 * g.Cout * conv3x3_fwd_blocks(g.N, g.H, g.W),
+                "partial must be fp32 [2*Cout*conv3x3_fwd_blocks(N, H, W)]");
+    partial_p = p.data_ptr<float>();
+  }
+  launch_conv3x3_fwd(x.data_ptr(), w.data_ptr(), out.data_ptr(), partial_p,
+                     g.N, g.H, g.W, g.Cin, g.Cout,
+                     at::cuda::getCurrentHIPStream().stream(),
+                     (int)phase_mask);
+}
+
+// dx [N,H,W,Cin] from dy [N,H,W,Cout] and the forward's w [Cout,3,3,Cin]:
+// repacks w into ``wflip_scratch`` (bf16, w's element count) as
+// [Cin,3,3,Cout], rotated, and runs the forward kernel on it.
+void conv3x3_dgrad(torch::Tensor dy, torch::Tensor w,
+                   torch::Tensor wflip_scratch, torch::Tensor dx,
+                   int64_t phase_mask = 7) {
+  const _C3Geom g = _check_conv3x3(dx, w, dy);
+  TORCH_CHECK(wflip_scratch.is_cuda() &&
+                  wflip_scratch.scalar_type() == torch::kBFloat16 &&
+                  wflip_scratch.is_contiguous() &&
+                  wflip_scratch.device() == w.device() &&
+                  wflip_scratch.numel() == w.numel(),
+              "wflip_scratch must be dense bf16 of w's size on w's device");
+  hipStream_t stream = at::cuda::getCurrentHIPStream().stream();
+  launch_conv3x3_wflip(w.data_ptr(), wflip_scratch.data_ptr(), g.Cin, g.Cout,
+                       stream);
+  launch_conv3x3_fwd(dy.data_ptr(), wflip_scratch.data_ptr(), dx.data_ptr(),
+                     nullptr, g.N, g.H, g.W, g.Cout, g.Cin, stream,
+                     (int)phase_mask);
+}
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
+  m.def("conv3x3_fwd", &conv3x3_fwd,
+        "MFMA 3x3/s1/p1 conv fwd (NHWC bf16), optional BN partial sums",
+        pybind11::arg("x"), pybind11::arg("w"), pybind11::arg("out"),
+        pybind11::arg("partial") = pybind11::none(),
+        pybind11::arg("phase_mask") = 7);
+  m.def("conv3x3_fwd_blocks", &conv3x3_fwd_blocks,
+        "M-block (= BN partial slot) count of the 3x3 conv fwd",
+        pybind11::arg("N"), pybind11::arg("H"), pybind11::arg("W"));
+  m.def("conv3x3_dgrad", &conv3x3_dgrad,
+        "MFMA 3x3/s1/p1 conv data-grad: weight repack + the fwd kernel",
+        pybind11::arg("dy"), pybind11::arg("w"),
+        pybind11::arg("wflip_scratch"), pybind11::arg("dx"),
+        pybind11::arg("phase_mask") = 7);
   m.def("conv1x1_s2_fwd", &conv1x1_s2_fwd,
         "MFMA pointwise stride-2 conv fwd (NHWC bf16), optional BN partials",
         pybind11::arg("x"), pybind11::arg("w"), pybind11::arg("out"),
