@@ -26,7 +26,7 @@ from ..ops.stemconv import StemConv2d
 
 def _conv3x3(cin: int, cout: int, stride: int = 1) -> nn.Conv2d:
     if stride == 1 and cin == cout:
-        # opt-in MFMA paths: forward + BN statistics and data-grad
+        # per-shape MFMA paths: forward + BN statistics and data-grad
         # (ops/csrc/conv3x3.hip), weight-grad (ops/csrc/conv3x3wrw.hip)
         return Conv3x3(cin, cout)
     return nn.Conv2d(cin, cout, 3, stride=stride, padding=1, bias=False)

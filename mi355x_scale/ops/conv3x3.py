@@ -1,7 +1,12 @@
 """3x3/s1/p1 conv: MFMA forward (with BN statistics), data-grad, weight-grad.
 
-Three independent legs, each opt-in and default-off; with every switch
-unset the conv is ``F.conv2d`` (MIOpen) in both directions.
+Three legs, each behind a tri-state switch read on every call: ``1``
+engages the leg wherever its gate allows, ``0`` never, and UNSET asks a
+small per-shape table in this file (``_FWD_TABLE``, ``_WRW_TABLE``), keyed
+on (C, H, W) with a batch floor, which holds only what was measured faster
+than MIOpen by the project's win rule. Everything the table does not name
+(every small-batch call among them) is ``F.conv2d`` (MIOpen) in both
+directions.
 
 Forward, ``MI355X_CONV3X3=1`` (``ops/csrc/conv3x3.hip``): an implicit GEMM
 in padded-flat coordinates. The input is seen as a zero-bordered map
@@ -21,26 +26,32 @@ the weight rotated and transposed. ``conv3x3_wflip_kernel`` repacks the
 weight (at most 4.7 MB) into a scratch tensor and the forward kernel runs
 on it; there is no second GEMM body.
 
-Weight-grad, ``MI355X_CONV_WRW=1`` (``ops/csrc/conv3x3wrw.hip``, Cin ==
-Cout, 9 <= W <= 64): MIOpen's weakest leg on these shapes, plus its
-fp32-workspace zero + bf16-cast launches and the AccumulateGrad add into
-the flat grad view. Inside hipGraph capture the cast kernel writes the
-weight's flat grad view DIRECTLY (the fused-BN fuse_acc pattern), so the
-add disappears from the captured step.
+Weight-grad, ``MI355X_CONV_WRW`` (``ops/csrc/conv3x3wrw.hip``, Cin == Cout,
+1 <= W <= 64): a split-K MFMA kernel in the same padded-flat coordinates.
+A block owns a 64 x 64 tile of dW for all nine taps and one chunk of
+32-pixel K-steps, stages dY panels and an LDS ring of X rows as they lie
+in memory, feeds both operands with transposed LDS reads and writes one
+fp32 partial per chunk; ``conv1x1_wrw_reduce_kernel`` sums the partials in
+a fixed order and rounds once to bf16. It replaces MIOpen's igemm wrw, its
+two fp32-workspace zero fills and its bf16 cast. While a graph is being
+captured and ``weight.grad`` is a bf16 channels-last tensor of the weight's
+shape (the FlatAdam views), the reduce ADDS into that view, bit for bit
+what ``AccumulateGrad``'s bf16 add of a returned ``dw`` produces, and
+backward returns ``None`` for the weight (the conv1x1 contract,
+ops/conv1x1.py, with the same caveats). Everywhere else backward returns a
+fresh ``dw``.
 
-STATUS, weight-grad (round 2, measured on MI355X —
-benchmarks/bench_conv3x3_wrw.py):
-numerics verified against the fp32 reference on every block-conv shape,
-but two blocking iterations both lost to MIOpen igemm wrw (v1 32x32
-tiles: 0.56x at C=64; v2 64x64 tiles / 8-wave blocks / non-atomic chunk
-partials: 0.35x at C=64 down to 0.10x at C=512). Ablations localize the
-cost to the thin per-row phase structure: one staging latency + three
-barriers per 56-px output row, at 1 block/CU (211 VGPRs -> 2
-waves/SIMD), cannot fill the machine, and the K-padding waste at
-W<=14 is fatal for layer3/4. Default-OFF (``MI355X_CONV_WRW=1`` opts
-in); the round-3 path is software-pipelined multi-row K-phases (stage
-row r+1 into registers during row r's MFMAs) plus a VGPR diet — see
-NOTES_NEXT.md.
+STATUS, weight-grad (one benchmark run on MI355X at batch 212, three
+alternating rounds, benchmarks/bench_conv3x3_wrw.py, tables in
+BASELINE.md): numerics are pinned to fp64 within one bf16 rounding
+(tests/test_conv3x3_wrw_flat.py). Kernel + reduce in accumulate mode
+against MIOpen wrw + the grad add, medians in us: 85 against 143 on 64@56,
+87 against 108 on 128@28, 93 against 105 on 256@14, 109 against 117 on
+512@7: FASTER on all four by the rule (slowest of ours 93.6 / 96.2 / 100.5
+/ 112.7 under MIOpen's fastest 139.4 / 107.6 / 104.6 / 116.5), so all four
+are in ``_WRW_TABLE`` at batch floor 212. Loads alone are 54-67 us, fragment
+reads + MFMA alone 55-72 us, epilogue + reduce 35 us (150 MB of fp32
+partials written and read back, the same for every shape).
 
 STATUS, forward and data-grad (one benchmark run on MI355X at batch 212,
 three alternating rounds — benchmarks/bench_conv3x3_fwd.py, table in
@@ -57,9 +68,13 @@ faster on all four (73 / 66 / 69 / 91 against 125 / 99 / 95 / 113).
 ResNet-18 step with both switches on: 6.98 / 6.94 / 7.00 ms against 7.62 /
 7.60 / 7.56 with them off (three alternating ``bench.py`` runs each):
 faster by the rule. Staging alone is 57-82 % of the call and MFMA alone
-50-69 %: the two do not overlap well yet (NOTES_NEXT.md lead 10). Both
-switches are default-OFF in this state: they are read on every call, and
-turning them on re-baselines the model's outputs.
+50-69 %: the two do not overlap well yet (NOTES_NEXT.md lead 10). Judged
+as a pair (``fwd + stats`` plus ``dgrad`` against MIOpen's ``fwd + reduce``
+plus ``dgrad``) all four shapes are faster by the rule, 256@14 included,
+and all four are in ``_FWD_TABLE`` at batch floor 212; the data-grad
+engages only where the forward did. The defaults re-baseline the model's
+outputs at batch >= 212 (profiles/r09_conv3x3_wrw_kernstats.md has the
+comparison against the parent's run-to-run spread).
 
 ``Conv3x3`` subclasses ``nn.Conv2d`` (state-dict compatible, same
 init). The forward / data-grad path takes CUDA bf16 channels-last inputs
@@ -77,28 +92,60 @@ import torch.nn.functional as F
 _S1 = ([1, 1], [1, 1], [1, 1], False, [0, 0], 1)  # stride, pad, dilation, ...
 
 
-def _switch(name: str) -> bool:
-    return os.environ.get(name, "0") == "1"
+# Per-shape defaults, (C, H, W) -> batch floor: what an UNSET switch engages.
+# A line is here only where the leg was measured faster at that batch by the
+# project's win rule (our slowest round under MIOpen's fastest); the floor
+# is the smallest batch measured. Forward and data-grad are judged as a
+# pair, ``fwd + stats`` plus ``dgrad`` against MIOpen's ``fwd + reduce``
+# plus ``dgrad``: BASELINE.md, "3x3 stride-1 conv MFMA kernels", slowest of
+# ours against MIOpen's fastest, us.
+_FWD_TABLE = {
+    (64, 56, 56): 212,   # 89.7 + 78.4 against 115.0 + 124.3
+    (128, 28, 28): 212,  # 76.2 + 67.4 against 83.0 + 97.5
+    (256, 14, 14): 212,  # 74.6 + 75.5 against 73.9 + 93.1 (fwd alone level)
+    (512, 7, 7): 212,    # 91.4 + 94.4 against 98.2 + 112.5
+}
+# Weight-grad + reduce in accumulate mode against MIOpen wrw + the grad add:
+# BASELINE.md, "3x3 stride-1 weight-grad".
+_WRW_TABLE = {
+    (64, 56, 56): 212,   # 93.6 against 139.4
+    (128, 28, 28): 212,  # 96.2 against 107.6
+    (256, 14, 14): 212,  # 100.5 against 104.6
+    (512, 7, 7): 212,    # 112.7 against 116.5
+}
+
+
+def _engaged(name: str, table: dict, c, n: int, h: int, w: int) -> bool:
+    """The tri-state rule of the three switches: ``1`` engages wherever the
+    gate allows, ``0`` never, unset asks ``table``."""
+    v = os.environ.get(name)
+    if v is not None:
+        return v == "1"
+    floor = table.get((c, h, w))
+    return floor is not None and n >= floor
 
 
 def _fwd_gate(x: torch.Tensor, weight: torch.Tensor) -> bool:
-    """True when ``MI355X_CONV3X3=1`` and conv3x3.hip takes this call."""
-    if not _switch("MI355X_CONV3X3") or not x.is_cuda:
+    """True when conv3x3.hip takes this call: ``MI355X_CONV3X3`` (or, unset,
+    the table) engages and the shape is inside the kernel's gate."""
+    if not x.is_cuda or x.dim() != 4 or weight.dim() != 4:
+        return False
+    n, cin, h, w = x.shape
+    cout = weight.shape[0]
+    # the table knows Cin == Cout shapes only
+    if not _engaged("MI355X_CONV3X3", _FWD_TABLE,
+                    cin if cin == cout else None, n, h, w):
         return False
     from . import HAVE_EXT, require_ext
-    ok = x.dim() == 4 and weight.dim() == 4
-    if ok:
-        n, cin, h, w = x.shape
-        cout = weight.shape[0]
-        ok = (tuple(weight.shape[1:]) == (cin, 3, 3)
-              and cin % 64 == 0 and 64 <= cin <= 2048
-              and cout % 64 == 0 and 64 <= cout <= 2048
-              and n >= 1 and h >= 1 and 1 <= w <= 64
-              and n * (h + 2) * (w + 2) + 2 * w + 6 < 2 ** 31
-              and x.dtype == torch.bfloat16
-              and weight.dtype == torch.bfloat16
-              and x.is_contiguous(memory_format=torch.channels_last)
-              and weight.is_contiguous(memory_format=torch.channels_last))
+    ok = (tuple(weight.shape[1:]) == (cin, 3, 3)
+          and cin % 64 == 0 and 64 <= cin <= 2048
+          and cout % 64 == 0 and 64 <= cout <= 2048
+          and n >= 1 and h >= 1 and 1 <= w <= 64
+          and n * (h + 2) * (w + 2) + 2 * w + 6 < 2 ** 31
+          and x.dtype == torch.bfloat16
+          and weight.dtype == torch.bfloat16
+          and x.is_contiguous(memory_format=torch.channels_last)
+          and weight.is_contiguous(memory_format=torch.channels_last))
     if ok and not HAVE_EXT:
         require_ext()  # asked for, and missing: no silent fallback
     return ok
@@ -137,10 +184,12 @@ def _backward(ctx, dy: torch.Tensor):
     """``(dx, dw)``: each leg on its HIP kernel or on aten, independently."""
     from . import _C
     x, weight = ctx.saved_tensors
-    if ctx.hip_fwd and dy.dtype != torch.bfloat16:
+    if (ctx.hip_fwd or ctx.hip_wrw) and dy.dtype != torch.bfloat16:
         dy = dy.to(torch.bfloat16)
     dy = dy.contiguous(memory_format=torch.channels_last)
-    hip_dgrad = ctx.hip_fwd and _switch("MI355X_CONV3X3_DGRAD")
+    n, c, h, w = x.shape
+    hip_dgrad = ctx.hip_fwd and _engaged("MI355X_CONV3X3_DGRAD", _FWD_TABLE,
+                                         c, n, h, w)
     need_dx, need_dw = ctx.needs_input_grad[:2]
     # whatever stays on aten goes in one call
     mask = [need_dx and not hip_dgrad, need_dw and not ctx.hip_wrw, False]
@@ -154,28 +203,38 @@ def _backward(ctx, dy: torch.Tensor):
                             device=weight.device)
         _C.conv3x3_dgrad(dy.permute(0, 2, 3, 1), weight.permute(0, 2, 3, 1),
                          wflip, dx.permute(0, 2, 3, 1))
-    if ctx.hip_wrw:
-        C = weight.shape[0]
-        nch = _C.conv3x3_wrw_nchunks(x.shape[0], x.shape[2], C, 0)
-        scratch = torch.empty(nch * C * 9 * C, dtype=torch.float32,
-                              device=x.device)
-        g = weight.grad
-        fuse = (torch.cuda.is_current_stream_capturing()
-                and g is not None and g.dtype == torch.bfloat16
-                and g.is_contiguous(memory_format=torch.channels_last))
-        dw = g if fuse else torch.empty_like(weight)
-        _C.conv3x3_wrw(x.permute(0, 2, 3, 1), dy.permute(0, 2, 3, 1),
-                       scratch, dw.permute(0, 2, 3, 1))
-        # fuse: the cast kernel wrote the flat grad view; returning None
-        # skips autograd's AccumulateGrad add for this weight
-        if fuse:
-            dw = None
+    if need_dw and ctx.hip_wrw:
+        dw = _wrw(x, dy, weight)
     return dx, dw
 
 
+def _wrw(x: torch.Tensor, dy: torch.Tensor, weight: torch.Tensor):
+    """Weight-grad on conv3x3wrw.hip. Returns a fresh ``dw``, or None after
+    adding it into ``weight.grad`` in place (under graph capture, when the
+    grad is a bf16 channels-last tensor of the weight's shape: the conv1x1
+    contract, ops/conv1x1.py)."""
+    from . import _C
+    n, c, h, w = x.shape
+    with torch.cuda.device(x.device):  # the chunk rule asks this device
+        nch = _C.conv3x3_wrw_nchunks(n, h, w, c)
+    part = torch.empty(nch * 9 * c * c, dtype=torch.float32, device=x.device)
+    xn, dyn = x.permute(0, 2, 3, 1), dy.permute(0, 2, 3, 1)
+    g = weight.grad
+    if (torch.cuda.is_current_stream_capturing() and g is not None
+            and g.dtype == torch.bfloat16 and g.device == weight.device
+            and g.shape == weight.shape
+            and g.is_contiguous(memory_format=torch.channels_last)):
+        _C.conv3x3_wrw(xn, dyn, part, g.permute(0, 2, 3, 1), True)
+        return None
+    dw = torch.empty_like(weight)
+    _C.conv3x3_wrw(xn, dyn, part, dw.permute(0, 2, 3, 1))
+    return dw
+
+
 class _Conv3x3Fn(torch.autograd.Function):
-    """The node of ``MI355X_CONV_WRW=1``: weight-grad on conv3x3wrw.hip;
-    forward and data-grad on conv3x3.hip where their switches engage."""
+    """The node of an engaged ``MI355X_CONV_WRW``: weight-grad on
+    conv3x3wrw.hip; forward and data-grad on conv3x3.hip where their
+    switches engage."""
 
     @staticmethod
     def forward(ctx, x: torch.Tensor, weight: torch.Tensor):
@@ -210,25 +269,31 @@ class _Conv3x3HipFn(torch.autograd.Function):
 
 
 class Conv3x3(nn.Conv2d):
-    """3x3/s1/p1 conv (no bias) with the opt-in MFMA HIP paths."""
+    """3x3/s1/p1 conv (no bias) with the per-shape MFMA HIP paths."""
 
     def __init__(self, cin: int, cout: int):
         super().__init__(cin, cout, 3, stride=1, padding=1, bias=False)
 
     def _hip_ok(self, x: torch.Tensor) -> bool:
-        """The weight-grad kernel's gate (``MI355X_CONV_WRW=1``)."""
-        from . import HAVE_EXT
+        """The weight-grad kernel's gate (``MI355X_CONV_WRW`` or the table)."""
+        if not x.is_cuda or x.dim() != 4:
+            return False
+        from . import HAVE_EXT, require_ext
         C = self.out_channels
-        return (HAVE_EXT and x.is_cuda
-                and _switch("MI355X_CONV_WRW")
-                and self.in_channels == C
-                and C % 64 == 0 and C <= 2048
-                and 9 <= x.shape[-1] <= 64
-                and x.dtype == torch.bfloat16
-                and self.weight.dtype == torch.bfloat16
-                and x.is_contiguous(memory_format=torch.channels_last)
-                and self.weight.is_contiguous(
-                    memory_format=torch.channels_last))
+        n, _, h, w = x.shape
+        ok = (_engaged("MI355X_CONV_WRW", _WRW_TABLE, C, n, h, w)
+              and self.in_channels == C and x.shape[1] == C
+              and C % 64 == 0 and C <= 2048
+              and n >= 1 and h >= 1 and 1 <= w <= 64
+              and n * (h + 2) * (w + 2) + 2 * w + 6 < 2 ** 31
+              and x.dtype == torch.bfloat16
+              and self.weight.dtype == torch.bfloat16
+              and x.is_contiguous(memory_format=torch.channels_last)
+              and self.weight.is_contiguous(
+                  memory_format=torch.channels_last))
+        if ok and not HAVE_EXT:
+            require_ext()  # asked for, and missing: no silent fallback
+        return ok
 
     def stats_ok(self, x: torch.Tensor) -> bool:
         """True when ``forward_with_stats`` will run the fused kernel."""

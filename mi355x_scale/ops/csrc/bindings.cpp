@@ -185,13 +185,6 @@ extern "C" void launch_stem_conv_wrw(const void* x, const void* dy,
                                      hipStream_t stream, int phase_mask,
                                      int tr);
 extern "C" int stem_wrw_scratch_elems();
-extern "C" void launch_conv3x3_wrw(const void* x, const void* dy,
-                                   float* part, void* dw_bf16,
-                                   int Nb, int H, int W, int C,
-                                   int chunks, hipStream_t stream,
-                                   int phase_mask);
-extern "C" int conv3x3_wrw_chunks(int Nb, int H, int C, int chunks_req);
-
 static void _check_f32(const torch::Tensor& t, const char* name) {
   TORCH_CHECK(t.is_cuda() && t.scalar_type() == torch::kFloat32 &&
                   t.is_contiguous(),
@@ -1107,36 +1100,6 @@ void stem_conv_wrw(torch::Tensor x, torch::Tensor dy, torch::Tensor dw_f32,
                        (int)phase_mask, tr ? 1 : 0);
 }
 
-// 3x3/s1/p1 CxC weight grad: part fp32 [chunks][C][9][C] scratch
-// (size via conv3x3_wrw_nchunks), dw bf16 out in channels_last weight
-// layout (may be the flat grad view).
-void conv3x3_wrw(torch::Tensor x, torch::Tensor dy, torch::Tensor part,
-                 torch::Tensor dw, int64_t phase_mask = 7,
-                 int64_t chunks = 0) {
-  TORCH_CHECK(x.is_cuda() && x.scalar_type() == torch::kBFloat16);
-  TORCH_CHECK(dy.is_cuda() && dy.scalar_type() == torch::kBFloat16);
-  int Nb = x.size(0), H = x.size(1), W = x.size(2), C = x.size(3);
-  TORCH_CHECK(dy.size(1) == H && dy.size(2) == W && dy.size(3) == C,
-              "same-shape 3x3 s1 conv only");
-  TORCH_CHECK(C % 64 == 0 && C <= 2048, "C must be a multiple of 64");
-  TORCH_CHECK(W >= 3 && W <= 64, "row length outside kernel bounds");
-  const int nch = conv3x3_wrw_chunks(Nb, H, C, (int)chunks);
-  TORCH_CHECK(part.scalar_type() == torch::kFloat32 &&
-              part.numel() >= (long long)nch * C * 9 * C,
-              "partial buffer too small for ", nch, " chunks");
-  TORCH_CHECK(dw.scalar_type() == torch::kBFloat16 &&
-              dw.numel() == (long long)C * 9 * C);
-  launch_conv3x3_wrw(x.data_ptr(), dy.data_ptr(), part.data_ptr<float>(),
-                     dw.data_ptr(), Nb, H, W, C, nch,
-                     at::cuda::getCurrentHIPStream().stream(),
-                     (int)phase_mask);
-}
-
-int64_t conv3x3_wrw_nchunks(int64_t Nb, int64_t H, int64_t C,
-                            int64_t chunks) {
-  return conv3x3_wrw_chunks((int)Nb, (int)H, (int)C, (int)chunks);
-}
-
 // Pointwise (1x1 s1) conv as a GEMM over raw NHWC storage (conv1x1.hip).
 extern "C" int conv1x1_m_blocks(long long M);
 extern "C" void launch_conv1x1_fwd(const void* x, const void* w, void* out,
@@ -1450,6 +1413,56 @@ void conv3x3_dgrad(torch::Tensor dy, torch::Tensor w,
                      (int)phase_mask);
 }
 
+extern "C" int conv3x3_wrw_chunks(long long Q, int C, int req);
+extern "C" void launch_conv3x3_wrw(const void* x, const void* dy, float* part,
+                                   void* dw, int N, int H, int W, int C,
+                                   int nchunks, int accumulate,
+                                   hipStream_t stream, int phase_mask);
+
+// Chunk count the 3x3 weight-grad uses for ``chunks`` (0 = the default
+// rule, which depends on the CU count of the CURRENT device): ``part``
+// holds exactly that many [C][3][3][C] fp32 slices.
+int64_t conv3x3_wrw_nchunks(int64_t N, int64_t H, int64_t W, int64_t C,
+                            int64_t chunks = 0) {
+  TORCH_CHECK(N >= 1 && N < (1LL << 31) && H >= 1 && H < (1LL << 24) &&
+                  W >= 1 && W <= 64 &&
+                  N * (H + 2) * (W + 2) + 2 * W + 6 < (1LL << 31) &&
+                  chunks >= 0 && chunks < (1LL << 31) && C % 64 == 0 &&
+                  C >= 64 && C <= 2048,
+              "conv3x3_wrw: N, H, W, C or chunks out of range");
+  const int n = conv3x3_wrw_chunks(N * (H + 2) * (W + 2), (int)C, (int)chunks);
+  TORCH_CHECK(n > 0, "conv3x3_wrw: cannot read the device's CU count");
+  return n;
+}
+
+// dw [C,3,3,C] (a channels-last [C,C,3,3] weight's physical view) from x and
+// dy [N,H,W,C], split over the virtual pixels into conv3x3_wrw_nchunks(...)
+// fp32 partials in ``part`` (every element is written: torch.empty serves)
+// and reduced in a second launch that rounds once to bf16. ``accumulate``:
+// add that rounded value into the bf16 values ``dw`` holds, as a bf16 tensor
+// add would (dw may be a flat grad view).
+void conv3x3_wrw(torch::Tensor x, torch::Tensor dy, torch::Tensor part,
+                 torch::Tensor dw, bool accumulate = false,
+                 int64_t chunks = 0, int64_t phase_mask = 7) {
+  const _C3Geom g = _check_conv3x3(x, dw, dy);
+  TORCH_CHECK(g.Cin == g.Cout, "conv3x3_wrw: needs Cin == Cout");
+  // the default chunk rule reads the CU count of the current device
+  const c10::DeviceGuard guard(x.device());
+  const int64_t nch = conv3x3_wrw_nchunks(g.N, g.H, g.W, g.Cin, chunks);
+  TORCH_CHECK(part.is_cuda() && part.scalar_type() == torch::kFloat32 &&
+                  part.is_contiguous() && part.device() == x.device() &&
+                  part.numel() == nch * 9 * g.Cin * g.Cin,
+              "part must be fp32 [conv3x3_wrw_nchunks*9*C*C] (", nch,
+              " chunks)");
+  TORCH_CHECK(nch * (g.Cin / 64) * (g.Cin / 64) < (1LL << 31),
+              "conv3x3_wrw: too many blocks for one launch");
+  launch_conv3x3_wrw(x.data_ptr(), dy.data_ptr(), part.data_ptr<float>(),
+                     dw.data_ptr(), g.N, g.H, g.W, g.Cin, (int)nch,
+                     accumulate ? 1 : 0,
+                     at::cuda::getCurrentHIPStream().stream(),
+                     (int)phase_mask);
+}
+
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("conv3x3_fwd", &conv3x3_fwd,
         "MFMA 3x3/s1/p1 conv fwd (NHWC bf16), optional BN partial sums",
@@ -1500,12 +1513,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         pybind11::arg("dy"), pybind11::arg("w"), pybind11::arg("dx"),
         pybind11::arg("phase_mask") = 7);
   m.def("conv3x3_wrw", &conv3x3_wrw,
-        "MFMA 3x3/s1 CxC weight grad (fp32 accum, bf16 cast to view)",
+        "MFMA 3x3/s1/p1 CxC conv weight-grad (split over the virtual pixels, "
+        "fp32 partials, bf16 store or accumulate into dw)",
         pybind11::arg("x"), pybind11::arg("dy"), pybind11::arg("part"),
-        pybind11::arg("dw"), pybind11::arg("phase_mask") = 7,
-        pybind11::arg("chunks") = 0);
+        pybind11::arg("dw"), pybind11::arg("accumulate") = false,
+        pybind11::arg("chunks") = 0, pybind11::arg("phase_mask") = 7);
   m.def("conv3x3_wrw_nchunks", &conv3x3_wrw_nchunks,
-        "partial-buffer chunk count the wrw launcher will use");
+        "chunk (= fp32 partial slice) count of the 3x3 weight-grad",
+        pybind11::arg("N"), pybind11::arg("H"), pybind11::arg("W"),
+        pybind11::arg("C"), pybind11::arg("chunks") = 0);
   m.def("stem_conv_fwd", &stem_conv_fwd,
         "MFMA stem conv fwd (7x7 s2, 3->64, NHWC bf16)",
         pybind11::arg("x"), pybind11::arg("w"), pybind11::arg("out"),

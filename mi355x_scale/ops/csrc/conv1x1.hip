@@ -79,7 +79,7 @@
 // S2 is a template parameter and the stride-1 geometry argument an empty
 // struct: the stride-1 instantiations compile to the code they had.
 #include <hip/hip_runtime.h>
-#include <hip/hip_bf16.h>
+#include "conv_mfma.h"
 
 #include <type_traits>
 
@@ -88,26 +88,11 @@
 #define BK 64                   // K-step
 #define OTROW 72                // epilogue tile row stride (els): 144 B
 
-typedef __bf16 bf16;
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(4))) short s16x4;
-typedef __attribute__((ext_vector_type(8))) short s16x8;
-
 enum { C1_FWD = 0, C1_FWD_STATS = 1, C1_DGRAD = 2 };
 
 // element offset of 16-byte chunk ``ch`` of row ``row`` in a [rows][BK] tile
 __device__ __forceinline__ int swz(int row, int ch) {
   return row * BK + ((ch ^ (row & 7)) << 3);
-}
-
-// one MFMA operand (8 K values per lane) from two transposed block reads
-__device__ __forceinline__ bf16x8 tr_frag(const bf16* p0, const bf16* p1) {
-  typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-  const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)p0);
-  const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)p1);
-  const s16x8 v = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-  return __builtin_bit_cast(bf16x8, v);
 }
 
 // Stride-2 geometry: the large map's H and W, the small map's Wo and
@@ -524,11 +509,6 @@ extern "C" void launch_conv1x1_s2_dgrad(const void* dy, const void* w,
 #define WPANEL (WK * 64)        // elements of one [WK][64] panel
 #define WRW_MIN_STEPS 4         // shortest chunk the default rule makes
 
-__device__ __forceinline__ int wswz(int row, int ch) {
-  const int f = (((row & 3) ^ ((row >> 3) & 1)) << 1) | ((row >> 2) & 1);
-  return row * 64 + ((ch ^ f) << 3);
-}
-
 // part[chunk][Cout][Cin] = sum over the chunk's rows. grid = chunks *
 // tiles; spc = K-steps per chunk (the last chunk may be shorter, never
 // empty). phase_mask: 1 = global loads + LDS staging, 4 = MFMA, 2 = epilogue.
@@ -711,6 +691,19 @@ __global__ __launch_bounds__(256) void conv1x1_wrw_reduce_kernel(
   *reinterpret_cast<bf16x4*>(dw + e0) = o;
 }
 
+// The reduce over ``nel`` elements (a multiple of 4096) of ``nchunks``
+// partials; conv3x3wrw.hip launches it for its [Cout][9][Cin] partials too.
+extern "C" void launch_conv_wrw_reduce(const float* part, void* dw,
+                                       long long nel, int nchunks,
+                                       int accumulate, hipStream_t stream) {
+  int groups = 1;  // about 16 chunks per thread, at most 16 groups
+  while (groups < 16 && nchunks > 16 * groups) groups *= 2;
+  hipLaunchKernelGGL(conv1x1_wrw_reduce_kernel,
+                     dim3((unsigned)(nel / (4 * (256 / groups)))), dim3(256),
+                     0, stream, part, (bf16*)dw, nel, nchunks, groups,
+                     accumulate);
+}
+
 static int wrw_side(int c) { return c % 128 == 0 ? 128 : 64; }
 
 static int wrw_tiles(int Cin, int Cout) {
@@ -762,13 +755,8 @@ static void wrw_launch(const void* x, const void* dy, float* part, void* dw,
   else if (tci == 128) W_LAUNCH(64, 128);
   else W_LAUNCH(64, 64);
 #undef W_LAUNCH
-  const long long nel = (long long)Cout * Cin;
-  int groups = 1;  // about 16 chunks per thread, at most 16 groups
-  while (groups < 16 && nchunks > 16 * groups) groups *= 2;
-  hipLaunchKernelGGL(conv1x1_wrw_reduce_kernel,
-                     dim3((unsigned)(nel / (4 * (256 / groups)))), block, 0,
-                     stream, part, (bf16*)dw, nel, nchunks, groups,
-                     accumulate);
+  launch_conv_wrw_reduce(part, dw, (long long)Cout * Cin, nchunks, accumulate,
+                         stream);
 }
 
 extern "C" void launch_conv1x1_wrw(const void* x, const void* dy, float* part,

@@ -67,7 +67,7 @@
 // blocks per CU; conv3x3_wflip_kernel 22 VGPRs, 9,216 B LDS, 8 waves per
 // SIMD. Scratch is 0 for all three.
 #include <hip/hip_runtime.h>
-#include <hip/hip_bf16.h>
+#include "conv_mfma.h"
 
 #define C3_BM 128               // virtual pixels per block
 #define C3_BN 64                // output channels per block
@@ -75,43 +75,9 @@
 #define C3_OTROW 72             // epilogue tile row stride (els): 144 B
 #define C3_MAXU 9               // 32-row staging passes: ceil(262 / 32)
 
-typedef __bf16 bf16;
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-
-// the padded map's row length and image size, floor(2^32 / d) for both,
-// and the virtual pixel count Q = N*(H+2)*(W+2) (below 2^31)
-struct C3Geo {
-  int H, W, Wp, HpWp, Q;
-  unsigned rWp, rHpWp;
-};
-
 // element offset of 16-byte chunk ``ch`` of row ``row`` in a [rows][64] tile
 __device__ __forceinline__ int c3_swz(int row, int ch) {
   return row * C3_BK + ((ch ^ (row & 7)) << 3);
-}
-
-// q = m / d, m -= q * d: m * floor(2^32/d) / 2^32 lies in (m/d - 1, m/d]
-__device__ __forceinline__ unsigned c3_divmod(unsigned& m, unsigned d,
-                                              unsigned rd) {
-  unsigned q = __umulhi(m, rd);
-  m -= q * d;
-  if (m >= d) {
-    m -= d;
-    ++q;
-  }
-  return q;
-}
-
-// virtual pixel q (any value) -> its row in the real map, or -1 on the
-// zero border and outside [0, Q)
-__device__ __forceinline__ int c3_pixel(long long q, const C3Geo& g) {
-  if (q < 0 || q >= g.Q) return -1;
-  unsigned m = (unsigned)q;
-  const unsigned n = c3_divmod(m, (unsigned)g.HpWp, g.rHpWp);
-  const unsigned hp = c3_divmod(m, (unsigned)g.Wp, g.rWp);  // m is now wp
-  if (hp - 1u >= (unsigned)g.H || m - 1u >= (unsigned)g.W) return -1;
-  return (int)((n * g.H + hp - 1u) * g.W + m - 1u);
 }
 
 // Y[pixel][Cout] over the virtual pixels, Wt = [Cout][9][Cin]. grid =
@@ -354,12 +320,6 @@ __global__ __launch_bounds__(256) void conv3x3_wflip_kernel(
   }
 }
 
-// floor(2^32 / d), saturated for d = 1: the multiplier c3_divmod takes
-static unsigned c3_recip(long long d) {
-  const long long r = (1LL << 32) / d;
-  return r > 0xffffffffLL ? 0xffffffffu : (unsigned)r;
-}
-
 // M-blocks (= statistics slots per channel): ceil(N*(H+2)*(W+2) / 128)
 extern "C" int conv3x3_m_blocks(long long N, long long H, long long W) {
   return (int)((N * (H + 2) * (W + 2) + C3_BM - 1) / C3_BM);
@@ -376,9 +336,7 @@ extern "C" void launch_conv3x3_fwd(const void* x, const void* w, void* out,
                                    float* partial, int N, int H, int W,
                                    int Cin, int Cout, hipStream_t stream,
                                    int phase_mask) {
-  const long long hpwp = (long long)(H + 2) * (W + 2);
-  const C3Geo g = {H, W, W + 2, (int)hpwp, (int)(N * hpwp),
-                   c3_recip(W + 2), c3_recip(hpwp)};
+  const C3Geo g = c3_geo(N, H, W);
   const int ntn = Cout / C3_BN;
   const dim3 grid(conv3x3_m_blocks(N, H, W) * ntn), block(256);
   const size_t lds = conv3x3_lds_bytes(W);

@@ -61,7 +61,8 @@ setup(
         CUDAExtension(
             name="mi355x_scale.ops._C",
             sources=SRC,
-            depends=["mi355x_scale/ops/csrc/groupfit.h"],
+            depends=["mi355x_scale/ops/csrc/groupfit.h",
+                     "mi355x_scale/ops/csrc/conv_mfma.h"],
             extra_compile_args={
                 "cxx": ["-O3"],
                 "nvcc": ["-O3", "--offload-arch=gfx950"],
