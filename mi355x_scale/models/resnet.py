@@ -29,6 +29,9 @@ def _conv3x3(cin: int, cout: int, stride: int = 1) -> nn.Conv2d:
         # per-shape MFMA paths: forward + BN statistics and data-grad
         # (ops/csrc/conv3x3.hip), weight-grad (ops/csrc/conv3x3wrw.hip)
         return Conv3x3(cin, cout)
+    if stride == 2:
+        # forward + BN statistics and data-grad (ops/csrc/conv3x3s2.hip)
+        return Conv3x3(cin, cout, 2)
     return nn.Conv2d(cin, cout, 3, stride=stride, padding=1, bias=False)
 
 
@@ -39,7 +42,7 @@ def _conv1x1(cin: int, cout: int, stride: int = 1) -> nn.Conv2d:
 
 def _conv_bn(conv: nn.Conv2d, bn: FusedBNReLU2d, x: torch.Tensor,
              residual: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """``bn(conv(x), residual)``. A pointwise or a stride-1 3x3 conv on its
+    """``bn(conv(x), residual)``. A pointwise or a 3x3 conv on its
     HIP path has already summed the BN's batch statistics in its epilogue,
     so the BN skips its reduce pass over the conv's output. Serves the
     main path and, through ``_Downsample``, the skip path."""

@@ -76,10 +76,41 @@ engages only where the forward did. The defaults re-baseline the model's
 outputs at batch >= 212 (profiles/r09_conv3x3_wrw_kernstats.md has the
 comparison against the parent's run-to-run spread).
 
+Stride 2 (``Conv3x3(cin, cout, stride=2)``, ``ops/csrc/conv3x3s2.hip``),
+behind switches of its own, ``MI355X_CONV3X3_S2`` (forward and statistics)
+and ``MI355X_CONV3X3_S2_DGRAD`` (only where the forward engaged), with
+``_S2_TABLE`` keyed (Cin, Cout, H, W); the three stride-1 switches never
+touch a stride-2 module. At stride 2 a tap is no constant offset in input
+coordinates, so the kernels work on the OUTPUT grid, seen as a virtual map
+``[N][Ho+1][Wo+1]`` with one leading zero row and column: the input splits
+into four parity planes ``X[2i+ph][2j+pw]``, and on that grid every tap is
+a constant offset into exactly one plane. The forward stages one plane
+band (``128 + Wo + 2`` rows) at a time into two alternating LDS buffers and
+runs that plane's 4, 2, 2 or 1 taps from it; the data-grad computes each
+parity plane of ``dX`` as a 4-, 2-, 2- or 1-tap convolution of one ``dY``
+band against the repacked weight and writes every ``dX`` pixel exactly
+once. Cin and Cout may differ, 1 <= W <= 128. The weight-grad of these
+convs stays on aten/MIOpen.
+
+STATUS, stride 2 (one benchmark run on MI355X at batch 212, three
+alternating rounds, benchmarks/bench_conv3x3_s2.py, table in BASELINE.md):
+numerics are pinned to fp64 references (tests/test_conv3x3_s2.py). Medians
+in us on 64->128@56 / 128->256@28 / 256->512@14 / 128->128@56 /
+256->256@28 / 512->512@14: forward + statistics 73 / 61 / 63 / 113 / 96 /
+111 against MIOpen + ``bn_fwd_reduce`` 60 / 53 / 62 / 92 / 78 / 101:
+SLOWER on all six, as is the plain forward (68 / 57 / 61 / 109 / 93 / 110
+against 46 / 40 / 52 / 81 / 70 / 93). The data-grad, repack included, is 87
+/ 60 / 59 / 165 / 106 / 105 against 89 / 63 / 62 / 133 / 114 / 111: LEVEL
+by the rule on five shapes, slower on 128->128@56. No pair wins, so
+``_S2_TABLE`` is empty and an unset switch means ``F.conv2d``, bit for bit
+what the module computed before. Loads + staging alone are 80-93 % of the
+forward call (NOTES_NEXT.md lead 1(d)).
+
 ``Conv3x3`` subclasses ``nn.Conv2d`` (state-dict compatible, same
 init). The forward / data-grad path takes CUDA bf16 channels-last inputs
 and a bf16 channels-last weight with Cin, Cout in {64, 128, ..., 2048} and
-1 <= W <= 64; everything else falls back to the standard conv autograd.
+1 <= W <= 64 (128 at stride 2); everything else falls back to the standard
+conv autograd.
 """
 from __future__ import annotations
 
@@ -90,6 +121,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 _S1 = ([1, 1], [1, 1], [1, 1], False, [0, 0], 1)  # stride, pad, dilation, ...
+_S2 = ([2, 2], [1, 1], [1, 1], False, [0, 0], 1)
 
 
 # Per-shape defaults, (C, H, W) -> batch floor: what an UNSET switch engages.
@@ -115,13 +147,19 @@ _WRW_TABLE = {
 }
 
 
+# Stride 2, (Cin, Cout, H, W) -> batch floor, judged as a pair in the same
+# way: BASELINE.md, "3x3 stride-2 conv MFMA kernels".
+_S2_TABLE = {}
+
+
 def _engaged(name: str, table: dict, c, n: int, h: int, w: int) -> bool:
-    """The tri-state rule of the three switches: ``1`` engages wherever the
-    gate allows, ``0`` never, unset asks ``table``."""
+    """The tri-state rule of the switches: ``1`` engages wherever the gate
+    allows, ``0`` never, unset asks ``table``. ``c`` is the channel part of
+    the table's key: one number, or ``(Cin, Cout)`` for ``_S2_TABLE``."""
     v = os.environ.get(name)
     if v is not None:
         return v == "1"
-    floor = table.get((c, h, w))
+    floor = table.get((*c, h, w) if isinstance(c, tuple) else (c, h, w))
     return floor is not None and n >= floor
 
 
@@ -231,6 +269,86 @@ def _wrw(x: torch.Tensor, dy: torch.Tensor, weight: torch.Tensor):
     return dw
 
 
+def _s2_gate(x: torch.Tensor, weight: torch.Tensor) -> bool:
+    """True when conv3x3s2.hip takes this stride-2 call: ``MI355X_CONV3X3_S2``
+    (or, unset, ``_S2_TABLE``) engages and the shape is inside the gate."""
+    if not x.is_cuda or x.dim() != 4 or weight.dim() != 4:
+        return False
+    n, cin, h, w = x.shape
+    cout = weight.shape[0]
+    if not _engaged("MI355X_CONV3X3_S2", _S2_TABLE, (cin, cout), n, h, w):
+        return False
+    from . import HAVE_EXT, require_ext
+    ok = (tuple(weight.shape[1:]) == (cin, 3, 3)
+          and cin % 64 == 0 and 64 <= cin <= 2048
+          and cout % 64 == 0 and 64 <= cout <= 2048
+          and n >= 1 and h >= 1 and 1 <= w <= 128
+          and n * ((h + 1) // 2 + 1) * ((w + 1) // 2 + 1)
+          + (w + 1) // 2 + 2 < 2 ** 31
+          and n * h * w < 2 ** 31
+          and x.dtype == torch.bfloat16
+          and weight.dtype == torch.bfloat16
+          and x.is_contiguous(memory_format=torch.channels_last)
+          and weight.is_contiguous(memory_format=torch.channels_last))
+    if ok and not HAVE_EXT:
+        require_ext()  # asked for, and missing: no silent fallback
+    return ok
+
+
+class _Conv3x3S2Fn(torch.autograd.Function):
+    """Stride-2 forward on conv3x3s2.hip, returning ``(out, partial)`` as
+    ``_Conv3x3HipFn`` does; data-grad on its kernel where
+    ``MI355X_CONV3X3_S2_DGRAD`` engages; weight-grad on aten."""
+
+    @staticmethod
+    def forward(ctx, x: torch.Tensor, weight: torch.Tensor, stats: bool):
+        from . import _C
+        n, _, h, w = x.shape
+        cout = weight.shape[0]
+        out = torch.empty((n, cout, (h + 1) // 2, (w + 1) // 2),
+                          dtype=torch.bfloat16, device=x.device,
+                          memory_format=torch.channels_last)
+        partial = None
+        if stats:
+            partial = torch.empty(
+                2 * cout * _C.conv3x3_s2_fwd_blocks(n, h, w),
+                dtype=torch.float32, device=x.device)
+            ctx.mark_non_differentiable(partial)
+        _C.conv3x3_s2_fwd(x.permute(0, 2, 3, 1), weight.permute(0, 2, 3, 1),
+                          out.permute(0, 2, 3, 1), partial)
+        ctx.save_for_backward(x, weight)
+        ctx.set_materialize_grads(False)
+        return out, partial
+
+    @staticmethod
+    def backward(ctx, dy, _dpartial):
+        if dy is None:
+            return None, None, None
+        from . import _C
+        x, weight = ctx.saved_tensors
+        if dy.dtype != torch.bfloat16:
+            dy = dy.to(torch.bfloat16)
+        dy = dy.contiguous(memory_format=torch.channels_last)
+        n, cin, h, w = x.shape
+        hip_dgrad = _engaged("MI355X_CONV3X3_S2_DGRAD", _S2_TABLE,
+                             (cin, weight.shape[0]), n, h, w)
+        need_dx, need_dw = ctx.needs_input_grad[:2]
+        # whatever stays on aten (the weight-grad always) goes in one call
+        mask = [need_dx and not hip_dgrad, need_dw, False]
+        dx = dw = None
+        if mask[0] or mask[1]:
+            dx, dw, _ = torch.ops.aten.convolution_backward(
+                dy, x, weight, None, *_S2, mask)
+        if need_dx and hip_dgrad:
+            dx = torch.empty_like(x)
+            wflip = torch.empty(weight.numel(), dtype=torch.bfloat16,
+                                device=weight.device)
+            _C.conv3x3_s2_dgrad(dy.permute(0, 2, 3, 1),
+                                weight.permute(0, 2, 3, 1), wflip,
+                                dx.permute(0, 2, 3, 1))
+        return dx, dw, None
+
+
 class _Conv3x3Fn(torch.autograd.Function):
     """The node of an engaged ``MI355X_CONV_WRW``: weight-grad on
     conv3x3wrw.hip; forward and data-grad on conv3x3.hip where their
@@ -269,14 +387,22 @@ class _Conv3x3HipFn(torch.autograd.Function):
 
 
 class Conv3x3(nn.Conv2d):
-    """3x3/s1/p1 conv (no bias) with the per-shape MFMA HIP paths."""
+    """3x3/p1 conv (no bias), stride 1 or 2, with the per-shape MFMA HIP
+    paths. A stride-2 module answers to ``MI355X_CONV3X3_S2`` and
+    ``MI355X_CONV3X3_S2_DGRAD`` only."""
 
-    def __init__(self, cin: int, cout: int):
-        super().__init__(cin, cout, 3, stride=1, padding=1, bias=False)
+    def __init__(self, cin: int, cout: int, stride: int = 1):
+        if stride not in (1, 2):
+            raise ValueError(f"Conv3x3: stride must be 1 or 2, not {stride}")
+        super().__init__(cin, cout, 3, stride=stride, padding=1, bias=False)
+
+    @property
+    def _s2(self) -> bool:
+        return self.stride[0] == 2
 
     def _hip_ok(self, x: torch.Tensor) -> bool:
         """The weight-grad kernel's gate (``MI355X_CONV_WRW`` or the table)."""
-        if not x.is_cuda or x.dim() != 4:
+        if self._s2 or not x.is_cuda or x.dim() != 4:
             return False
         from . import HAVE_EXT, require_ext
         C = self.out_channels
@@ -297,17 +423,25 @@ class Conv3x3(nn.Conv2d):
 
     def stats_ok(self, x: torch.Tensor) -> bool:
         """True when ``forward_with_stats`` will run the fused kernel."""
+        if self._s2:
+            return _s2_gate(x, self.weight)
         return _fwd_gate(x, self.weight)
 
     def forward_with_stats(self, x: torch.Tensor):
         """``(conv(x), partial)``: ``partial`` holds the per-block BN sums
         of the output for ``FusedBNReLU2d.forward(..., partial=...)``, or
         is None when the HIP forward does not engage."""
+        if self._s2 and self.stats_ok(x):
+            return _Conv3x3S2Fn.apply(x, self.weight, True)
         if self.stats_ok(x):
             return _Conv3x3HipFn.apply(x, self.weight, True, self._hip_ok(x))
         return self.forward(x), None
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
+        if self._s2:
+            if self.stats_ok(x):
+                return _Conv3x3S2Fn.apply(x, self.weight, False)[0]
+            return F.conv2d(x, self.weight, None, 2, 1)
         if self.stats_ok(x):
             return _Conv3x3HipFn.apply(x, self.weight, False,
                                        self._hip_ok(x))[0]

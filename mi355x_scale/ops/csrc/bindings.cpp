@@ -1413,6 +1413,100 @@ void conv3x3_dgrad(torch::Tensor dy, torch::Tensor w,
                      (int)phase_mask);
 }
 
+// 3x3 / stride 2 / pad 1 conv over raw NHWC storage (conv3x3s2.hip): forward
+// (optionally with BN partial sums) and data-grad on the repacked weight.
+extern "C" int conv3x3_s2_m_blocks(long long N, long long H, long long W);
+extern "C" void launch_conv3x3_s2_fwd(const void* x, const void* w, void* out,
+                                      float* partial, int N, int H, int W,
+                                      int Cin, int Cout, hipStream_t stream,
+                                      int phase_mask);
+extern "C" void launch_conv3x3_s2_dgrad(const void* dy, const void* wf,
+                                        void* dx, int N, int H, int W,
+                                        int Cin, int Cout, hipStream_t stream,
+                                        int phase_mask);
+
+// xi [N,H,W,Cin], w [Cout,3,3,Cin], xo [N,(H+1)/2,(W+1)/2,Cout]: dense bf16
+// on one GPU, inside the gate
+static _C3Geom _check_conv3x3_s2(const torch::Tensor& xi,
+                                 const torch::Tensor& w,
+                                 const torch::Tensor& xo) {
+  for (const torch::Tensor* t : {&xi, &w, &xo})
+    TORCH_CHECK(t->is_cuda() && t->scalar_type() == torch::kBFloat16 &&
+                    t->is_contiguous() && t->device() == xi.device() &&
+                    t->dim() == 4,
+                "conv3x3_s2: dense 4-d bf16 GPU tensors on one device");
+  const int64_t N = xi.size(0), H = xi.size(1), W = xi.size(2);
+  const int64_t Cin = xi.size(3), Cout = xo.size(3);
+  TORCH_CHECK(Cin % 64 == 0 && Cin >= 64 && Cin <= 2048 &&
+                  Cout % 64 == 0 && Cout >= 64 && Cout <= 2048,
+              "conv3x3_s2: Cin and Cout must be multiples of 64 up to 2048");
+  TORCH_CHECK(w.size(0) == Cout && w.size(1) == 3 && w.size(2) == 3 &&
+                  w.size(3) == Cin,
+              "conv3x3_s2: weight must be [Cout, 3, 3, Cin]");
+  TORCH_CHECK(N >= 1 && H >= 1 && W >= 1 && W <= 128,
+              "conv3x3_s2: needs 1 <= W <= 128, H >= 1, N >= 1");
+  const int64_t Ho = (H + 1) / 2, Wo = (W + 1) / 2;
+  TORCH_CHECK(xo.size(0) == N && xo.size(1) == Ho && xo.size(2) == Wo,
+              "conv3x3_s2: the small map must be [N, (H+1)/2, (W+1)/2, Cout]");
+  // virtual pixels plus the band's halo, and the large map's pixel index
+  TORCH_CHECK(N < (1LL << 31) && H < (1LL << 24) &&
+                  N * (Ho + 1) * (Wo + 1) + Wo + 2 < (1LL << 31) &&
+                  N * H * W < (1LL << 31),
+              "conv3x3_s2: too many pixels for one launch");
+  return {(int)N, (int)H, (int)W, (int)Cin, (int)Cout};
+}
+
+int64_t conv3x3_s2_fwd_blocks(int64_t N, int64_t H, int64_t W) {
+  return conv3x3_s2_m_blocks(N, H, W);
+}
+
+// out = conv(x, w), stride 2, pad 1. With ``partial`` (fp32, 2*Cout*
+// conv3x3_s2_fwd_blocks(N, H, W) elements) the kernel also leaves the BN
+// channel sums of the values it stores, [2C][nblocks] as bn_fwd_finalize
+// reads them.
+void conv3x3_s2_fwd(torch::Tensor x, torch::Tensor w, torch::Tensor out,
+                    c10::optional<torch::Tensor> partial = c10::nullopt,
+                    int64_t phase_mask = 7) {
+  const _C3Geom g = _check_conv3x3_s2(x, w, out);
+  float* partial_p = nullptr;
+  if (partial.has_value()) {
+    const torch::Tensor& p = *partial;
+    TORCH_CHECK(p.is_cuda() && p.scalar_type() == torch::kFloat32 &&
+                    p.is_contiguous() && p.device() == x.device() &&
+                    p.numel() ==
+                        2 * g.Cout * conv3x3_s2_fwd_blocks(g.N, g.H, g.W),
+                "partial must be fp32 "
+                "[2*Cout*conv3x3_s2_fwd_blocks(N, H, W)]");
+    partial_p = p.data_ptr<float>();
+  }
+  launch_conv3x3_s2_fwd(x.data_ptr(), w.data_ptr(), out.data_ptr(), partial_p,
+                        g.N, g.H, g.W, g.Cin, g.Cout,
+                        at::cuda::getCurrentHIPStream().stream(),
+                        (int)phase_mask);
+}
+
+// dx [N,H,W,Cin] from dy [N,Ho,Wo,Cout] and the forward's w [Cout,3,3,Cin]:
+// repacks w into ``wflip_scratch`` (bf16, w's element count) as
+// [Cin,3,3,Cout], rotated, and runs the four dX planes on it. Every element
+// of dx is written (torch.empty serves).
+void conv3x3_s2_dgrad(torch::Tensor dy, torch::Tensor w,
+                      torch::Tensor wflip_scratch, torch::Tensor dx,
+                      int64_t phase_mask = 7) {
+  const _C3Geom g = _check_conv3x3_s2(dx, w, dy);
+  TORCH_CHECK(wflip_scratch.is_cuda() &&
+                  wflip_scratch.scalar_type() == torch::kBFloat16 &&
+                  wflip_scratch.is_contiguous() &&
+                  wflip_scratch.device() == w.device() &&
+                  wflip_scratch.numel() == w.numel(),
+              "wflip_scratch must be dense bf16 of w's size on w's device");
+  hipStream_t stream = at::cuda::getCurrentHIPStream().stream();
+  launch_conv3x3_wflip(w.data_ptr(), wflip_scratch.data_ptr(), g.Cin, g.Cout,
+                       stream);
+  launch_conv3x3_s2_dgrad(dy.data_ptr(), wflip_scratch.data_ptr(),
+                          dx.data_ptr(), g.N, g.H, g.W, g.Cin, g.Cout, stream,
+                          (int)phase_mask);
+}
+
 extern "C" int conv3x3_wrw_chunks(long long Q, int C, int req);
 extern "C" void launch_conv3x3_wrw(const void* x, const void* dy, float* part,
                                    void* dw, int N, int H, int W, int C,
@@ -1474,6 +1568,19 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         pybind11::arg("N"), pybind11::arg("H"), pybind11::arg("W"));
   m.def("conv3x3_dgrad", &conv3x3_dgrad,
         "MFMA 3x3/s1/p1 conv data-grad: weight repack + the fwd kernel",
+        pybind11::arg("dy"), pybind11::arg("w"),
+        pybind11::arg("wflip_scratch"), pybind11::arg("dx"),
+        pybind11::arg("phase_mask") = 7);
+  m.def("conv3x3_s2_fwd", &conv3x3_s2_fwd,
+        "MFMA 3x3/s2/p1 conv fwd (NHWC bf16), optional BN partial sums",
+        pybind11::arg("x"), pybind11::arg("w"), pybind11::arg("out"),
+        pybind11::arg("partial") = pybind11::none(),
+        pybind11::arg("phase_mask") = 7);
+  m.def("conv3x3_s2_fwd_blocks", &conv3x3_s2_fwd_blocks,
+        "M-block (= BN partial slot) count of the 3x3 stride-2 conv fwd",
+        pybind11::arg("N"), pybind11::arg("H"), pybind11::arg("W"));
+  m.def("conv3x3_s2_dgrad", &conv3x3_s2_dgrad,
+        "MFMA 3x3/s2/p1 conv data-grad: weight repack + the four dx planes",
         pybind11::arg("dy"), pybind11::arg("w"),
         pybind11::arg("wflip_scratch"), pybind11::arg("dx"),
         pybind11::arg("phase_mask") = 7);

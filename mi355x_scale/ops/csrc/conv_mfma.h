@@ -1,6 +1,7 @@
 // What the MFMA conv kernels share (conv1x1.hip, conv3x3.hip,
-// conv3x3wrw.hip): operand types, the transposed LDS fragment read with its
-// panel swizzle, and the padded-flat geometry of the 3x3 kernels.
+// conv3x3wrw.hip, conv3x3s2.hip): operand types, the transposed LDS fragment
+// read with its panel swizzle, and the padded-flat geometry of the 3x3
+// kernels, stride 1 and stride 2.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <hip/hip_bf16.h>
@@ -70,4 +71,35 @@ static inline C3Geo c3_geo(int N, int H, int W) {
   const long long hpwp = (long long)(H + 2) * (W + 2);
   return {H, W, W + 2, (int)hpwp, (int)(N * hpwp),
           c3_recip(W + 2), c3_recip(hpwp)};
+}
+
+// Padded-flat coordinates of a 3x3 / stride 2 / pad 1 conv: the OUTPUT grid
+// [N][Ho][Wo], Ho = (H+1)/2, Wo = (W+1)/2, is seen as a virtual map
+// [N][Ho+1][Wo+1] with one leading zero row and column per image, flat index
+// q = (n*(Ho+1) + ho+1)*Wp + wo+1, Wp = Wo+1. The four parity planes of the
+// input, P[ph][pw][i][j] = X[2i+ph][2j+pw], lie on the same grid. Row length
+// and image size of the virtual map, floor(2^32 / d) for both, and the
+// virtual pixel count Q = N*(Ho+1)*Wp (below 2^31).
+struct C3S2Geo {
+  int H, W, Ho, Wo, Wp, HpWp, Q;
+  unsigned rWp, rHpWp;
+};
+
+// virtual pixel q (any value) -> its cell (n, i, j) of the output grid (and
+// of every parity plane); false on the zero border and outside [0, Q)
+__device__ __forceinline__ bool c3s2_cell(long long q, const C3S2Geo& g,
+                                          int& n, int& i, int& j) {
+  if (q < 0 || q >= g.Q) return false;
+  unsigned m = (unsigned)q;
+  n = (int)c3_divmod(m, (unsigned)g.HpWp, g.rHpWp);
+  i = (int)c3_divmod(m, (unsigned)g.Wp, g.rWp) - 1;  // m is now wo + 1
+  j = (int)m - 1;
+  return i >= 0 && j >= 0;
+}
+
+static inline C3S2Geo c3s2_geo(int N, int H, int W) {
+  const int Ho = (H + 1) / 2, Wo = (W + 1) / 2;
+  const long long hpwp = (long long)(Ho + 1) * (Wo + 1);
+  return {H, W, Ho, Wo, Wo + 1, (int)hpwp, (int)(N * hpwp),
+          c3_recip(Wo + 1), c3_recip(hpwp)};
 }

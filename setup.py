@@ -28,6 +28,7 @@ SRC = [
     "mi355x_scale/ops/csrc/conv3x3wrw.hip",
     "mi355x_scale/ops/csrc/conv1x1.hip",
     "mi355x_scale/ops/csrc/conv3x3.hip",
+    "mi355x_scale/ops/csrc/conv3x3s2.hip",
 ]
 
 ASAN = os.environ.get("MI355X_ASAN") == "1"
